@@ -1,6 +1,32 @@
 """Benchmark of the path-tracing hot path (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c4|c5] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: setup, W warmup
+steps, the K timed steps, the outputs of the last timed step written to DIR
+(--dump-outputs), and the result line (metric, value, unit, ms_per_step, the
+configuration, the setup times and the kernel time of the timed steps).
+Everything else described below -- the comparison with the oracle's fixtures
+(`rmse`, `bit_exact`, `quality`, `reduced_frame_parity`), the one-GPU anchor of
+a process group and its checks (--check), `first_render_ms`, `one_shot`,
+`scaling_anchors`, the live-bounce count behind `roofline`, `roofline_valu`
+and the CPU baselines -- takes renders or CPU work of its own and runs only
+with --full; a plain line carries null in those places.
+
+--dump-outputs DIR: after the timed steps rank 0 writes the canvas the last
+timed step produced (what a caller of the timed path receives: float32 sums
+[nx*ny, 4], reduced over the ranks) as DIR/canvas.npy.  Every file holds
+finite numbers only: a sum that is not finite (the reference's NaN pixels: a
+non-finite attenuation, MapperPathTracer.cxx:350; 670 of C2's 640 000) is
+written as 0, as NormalizeFunctor writes it, and DIR/canvas_nonfinite.npy
+(float64 [k, 2]) lists each one: its flat index in canvas.npy and 1 for NaN,
+2 for +inf, 3 for -inf.  A canvas above 32 MB (C5) is written as a fixed,
+seeded sample of its pixels, with the sampled pixel indices in
+DIR/canvas_pixels.npy (float64); all files together stay within 64 MB.
+--steps 0 has no timed step to write: the two together are refused.  The
+scene, the camera and the per-pixel seeds are deterministic: the same
+arguments give the same file.
 
 One step = one full render of the workload's frame.  On one GPU (no process
 group) the frame goes through the library's default contiguous launch
@@ -24,18 +50,19 @@ N > 1 (launched by torch.distributed.run, one process per GPU):
       step's render (two canvases, alternating).
   --scaling weak: every rank renders a full nx x ny band of an nx x ny*N
       canvas (per-GPU work fixed).
-  After the timed region rank 0 renders the same workload's whole frame alone
-  (--anchor, default on): `one_gpu_same_workload` and
+  --full: after the timed region rank 0 renders the same workload's whole frame
+  alone (--anchor, default on): `one_gpu_same_workload` and
   `speedup_vs_one_gpu_same_workload` compare like with like (the driver's
-  N-GPU / 1-GPU ratio divides C5's rate by C2's).  The N = 1 line carries
-  `scaling_anchors`: one-GPU kernel times of C4's whole frame and of one C5
+  N-GPU / 1-GPU ratio divides C5's rate by C2's).  --full: the N = 1 line
+  carries `scaling_anchors`: one-GPU kernel times of C4's whole frame and of one C5
   rank share, measured in the same run.
 
 Rank 0 prints one JSON line.  `value` = all ranks' samples / max-over-ranks
 wall time of the K timed steps (steady state: the renderer's context, scene
-and RNG jump tables are set up before the timed region -- `setup` and
-`first_render_ms` report what that costs, and `one_shot` what a fresh process
-rendering once, like main.cc, would see).  `rmse` / `bit_exact` compare the
+and RNG jump tables are set up before the timed region -- `setup` and,
+with --full, `first_render_ms` report what that costs, and `one_shot` what a
+fresh process rendering once, like main.cc, would see).  The rest of this
+paragraph is --full only (null in a plain line).  `rmse` / `bit_exact` compare the
 last timed frame (normalised, NormalizeFunctor) with the oracle's committed
 C2 frame (tests/golden/c2_full.npz); at N > 1 the C5 line takes them from
 `reduced_frame_parity`: every rank's shard and the reduced frame at 1024
@@ -43,13 +70,15 @@ pixels against the oracle's reduced-frame fixture of that N
 (tests/golden/c5_reduced.npz, N = 2/4/8; bit-exact shards, the reduced frame
 bit-exact against the shards' sum in the reduce's fixed association), plus the
 statistical check of the reduced frame against an independent single-stream
-image.  `bench.py --gpus N` without torch.distributed.run starts it (one
-process per GPU) as a child and relays rank 0's line.  `roofline` prices the render kernel
+image.  `roofline` prices the render kernel
 with the SoA byte model of SURVEY.md 8(d) (56 + 88*L bytes per sample) against
 the 8 TB/s HBM peak; `roofline_valu` gives the VALU-issue bound (the one that
 binds) from the committed PMC summary; `cpu_baseline` times
 the oracle's stage-structured restatement on a bounded sample of the same
 workload on this host.
+
+`bench.py --gpus N` without torch.distributed.run starts it (one process per
+GPU) as a child and relays rank 0's line.
 """
 from __future__ import annotations
 
@@ -80,6 +109,48 @@ WORKLOADS = {
 SHARD = {"c2": "tiles", "c4": "tiles", "c5": "samples"}
 # pixels of the C5 frame compared with the single-stream image (statistical check)
 C5_CHECK_PIXELS = 65536
+# --dump-outputs: most bytes written in all; a larger canvas is sampled (seeded)
+DUMP_MAX_BYTES = 64 * 10**6
+DUMP_SEED = 20
+
+
+def dump_outputs(path: str, canvas) -> dict:
+    """Write the canvas of the last timed step (a torch tensor [nx*ny, 4],
+    float32) as path/canvas.npy, its non-finite sums written as 0, and
+    path/canvas_nonfinite.npy (float64 [k, 2]: the flat index of each such
+    value in canvas.npy and its code, 1 NaN, 2 +inf, 3 -inf; k = 0 when all
+    are finite); above DUMP_MAX_BYTES in all, a fixed, seeded sample of the
+    pixels (sorted) and their indices as canvas_pixels.npy (float64: exact
+    below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    n, row = canvas.shape[0], canvas.shape[1] * 4
+    written = {}
+    if n * row <= DUMP_MAX_BYTES // 2:
+        arr = canvas.cpu().numpy()
+    else:
+        import torch
+
+        # half of the budget: the list of non-finite values (16 bytes each)
+        # fits beside the sample even if most of a 4-byte value's were listed
+        keep = (DUMP_MAX_BYTES // 2) // (row + 8)
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        arr = canvas.index_select(0, torch.from_numpy(pix).to(canvas.device)).cpu().numpy()
+        np.save(os.path.join(path, "canvas_pixels.npy"), pix.astype(np.float64))
+        written["canvas_pixels"] = [int(keep)]
+    arr = np.array(arr, dtype=np.float32)
+    flat = arr.reshape(-1)
+    where = np.flatnonzero(~np.isfinite(flat))
+    vals = flat[where]
+    code = np.where(np.isnan(vals), 1.0, np.where(vals > 0, 2.0, 3.0))
+    marks = np.stack([where.astype(np.float64), code], axis=1) if where.size else np.zeros((0, 2), np.float64)
+    if marks.nbytes > DUMP_MAX_BYTES // 2 - 1024:
+        raise RuntimeError(f"--dump-outputs: {where.size} non-finite values in the canvas: not a frame")
+    flat[where] = 0
+    np.save(os.path.join(path, "canvas.npy"), arr)
+    np.save(os.path.join(path, "canvas_nonfinite.npy"), marks)
+    written["canvas"] = list(arr.shape)
+    written["canvas_nonfinite"] = list(marks.shape)
+    return written
 
 
 def cpu_baseline(budget_s: float, nx: int, ny: int, depth: int, nthreads: int = 1) -> dict:
@@ -422,7 +493,19 @@ def main() -> None:
                     help="one GPU, no process group: contig = the whole frame through the library's default launch "
                          "(rtp_render_device over [0, nx*ny), like main.cc's render); tiles = the tile-deal instance "
                          "the ranks of an N-GPU run use (rank 0 of 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps rank 0 writes the last timed step's canvas as DIR/canvas.npy "
+                         "(float32, non-finite sums as 0 and listed in DIR/canvas_nonfinite.npy; a canvas above 32 MB "
+                         "as a fixed, seeded pixel sample and DIR/canvas_pixels.npy); needs --steps >= 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the comparison with the oracle's "
+                         "fixtures, the one-GPU anchor and --check, the first-render and one-shot times, the "
+                         "scaling anchors, the live-bounce count of the roofline and the CPU baselines")
     args = ap.parse_args()
+    if not args.full and (args.check or args.scaling_anchors == "on"):
+        ap.error("--check and --scaling-anchors on take renders of their own: add --full")
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs writes the last timed step's canvas: it needs --steps >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: torch.distributed.run as a fresh child, before
         # anything here touches the GPU; never a one-GPU line for --gpus N
@@ -540,20 +623,23 @@ def main() -> None:
         return gather_canvas()
 
     # (the first frame after setup is timed on one GPU only: at N > 1 a C5
-    # frame takes seconds, and the warmup renders it anyway)
+    # frame takes seconds, and the warmup renders it anyway; --full)
     beat.phase = "first render and warmup"
     t_first = time.perf_counter()
-    if world == 1:
+    if world == 1 and args.full:
         render()
     torch.cuda.synchronize()
     t_first_done = time.perf_counter()
-    for i in range(args.warmup):  # the first also counts live bounces (for the byte model)
-        step(count_live=(i == 0))
-    if args.warmup == 0:
+    # --full: the first warmup step also counts live bounces (for the byte
+    # model), through the list / contiguous launch; a plain run warms up with
+    # the timed path alone
+    for i in range(args.warmup):
+        step(count_live=(args.full and i == 0))
+    if args.warmup == 0 and args.full:
         step(count_live=True)
     drain()
     torch.cuda.synchronize()
-    live_total = int(live.to(torch.int64).sum().item())
+    live_total = int(live.to(torch.int64).sum().item()) if args.full else None
 
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     if grouped:
@@ -574,13 +660,19 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if args.steps else float("nan")
 
-    # ---- after the timed region: checks and the same-workload one-GPU anchor ----
+    # ---- after the timed region: the outputs of the last timed step ----
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        beat.phase = "writing the outputs"
+        dumped = dump_outputs(args.dump_outputs, canvas)
+
+    # ---- --full: checks and the same-workload one-GPU anchor ----
     beat.phase = "checks and the one-GPU anchor"
     coll_dev = "cuda" if args.dist_backend == "nccl" else "cpu"
     quality = None
     parity = None
     gathered = None
-    if samples:
+    if samples and args.full:
         # (a) every rank's shard at the pixels of the oracle's reduced-frame
         # fixture of this world size (tools/make_golden_reduced.py), gathered
         # to rank 0 with the reduced frame there (reduced_frame_parity)
@@ -610,7 +702,7 @@ def main() -> None:
     one_gpu = None
     check = None
     want_anchor = grouped and args.anchor == "on"
-    if rank == 0 and (want_anchor or args.check):
+    if rank == 0 and args.full and (want_anchor or args.check):
         # rank 0 renders the same workload's whole frame alone: the one-GPU
         # time of this workload (the others wait at the barrier below)
         # sample batches: the anchor renders on a stream no rank uses
@@ -666,7 +758,7 @@ def main() -> None:
     # statistics of the timed instance stay the timed renders'.
     beat.phase = "one-shot render and scaling anchors"
     off_ms = float("nan")
-    if world == 1:
+    if world == 1 and args.full:
         dev.set_ff_tables("off")
         full_off = torch.empty((nx * ny, 4), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
@@ -681,16 +773,16 @@ def main() -> None:
         del full_off
         dev.set_ff_tables(args.ff_tables)
     anchors = None
-    if world == 1 and not grouped and (args.scaling_anchors == "on" or (
+    if args.full and world == 1 and not grouped and (args.scaling_anchors == "on" or (
             args.scaling_anchors == "auto" and workload == "c2" and sized)):
         anchors = scaling_anchors(dev, cam, stream.cuda_stream)
-    if rank == 0 and not samples:
+    if rank == 0 and args.full and not samples:
         gold = load_golden_frame(args.golden)
         if gold and (gold["nx"], gold["ny"], gold["spp"], gold["depth"]) == (nx, ny, args.spp, args.depth):
             quality = frame_quality(canvas.cpu().numpy(), gold, args.spp)
     kernel_ms_max = kernel_ms
     if grouped:
-        t = torch.tensor([elapsed, live_total, kernel_ms], dtype=torch.float64, device=coll_dev)
+        t = torch.tensor([elapsed, live_total or 0, kernel_ms], dtype=torch.float64, device=coll_dev)
         mx = t.clone()
         dist.all_reduce(mx, op=dist.ReduceOp.MAX)
         tot = t.clone()
@@ -699,17 +791,28 @@ def main() -> None:
         kernel_ms_max = float(mx[2].item())
         live_all = float(tot[1].item())
     else:
-        live_all = float(live_total)
+        live_all = float(live_total or 0)
 
     samples_rank = npix * spp_mine
     samples_all = nx * ny * args.spp
     value = samples_all * args.steps / elapsed / 1e6
-    L = live_all / samples_all
-    bytes_per_sample = 56.0 + 88.0 * L
-    achieved = samples_rank * bytes_per_sample / (kernel_ms / 1e3) / 1e9
-    cfg = {"nx": nx, "ny": args.ny, "spp": args.spp, "depth": args.depth}
-    traffic = load_traffic(args.traffic_json, cfg) if world == 1 else None
-    valu = load_valu(args.valu_json, cfg, kernel_ms) if world == 1 else None
+    roofline = valu = L = None
+    if args.full:  # the byte model needs the live-bounce count of the --full warmup
+        L = live_all / samples_all
+        bytes_per_sample = 56.0 + 88.0 * L
+        achieved = samples_rank * bytes_per_sample / (kernel_ms / 1e3) / 1e9
+        cfg = {"nx": nx, "ny": args.ny, "spp": args.spp, "depth": args.depth}
+        valu = load_valu(args.valu_json, cfg, kernel_ms) if world == 1 else None
+        roofline = {
+            "bound": "hbm",
+            "achieved": round(achieved, 3),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 6),
+            "traffic": load_traffic(args.traffic_json, cfg) if world == 1 else None,
+            "kernel_ms": round(kernel_ms, 3),
+            "bytes_per_sample_model": round(bytes_per_sample, 3),
+        }
     setup = {
         "context_ms": round((t_ctx - t_setup) * 1e3, 2),
         "scene_ms": round((t_scene - t_ctx) * 1e3, 2),
@@ -717,7 +820,7 @@ def main() -> None:
         "ff_tables": {k: ff[k] for k in ("policy", "built", "chain_tables", "direct_first", "direct_count")}
                      | {"gib": round(ff["bytes"] / 2**30, 1), "alloc_ms": round(ff["alloc_ms"], 1),
                         "build_ms": round(ff["build_ms"], 1),
-                        "render_ms_without": round(off_ms, 2) if world == 1 else None,
+                        "render_ms_without": round(off_ms, 2) if world == 1 and args.full else None,
                         "per_rank": (f"every rank builds its own tables on its own GPU before its first frame "
                                      f"({round(ff['bytes'] / 2**30, 1)} GiB of each GPU's HBM; this line: rank 0's "
                                      f"setup)") if grouped else None},
@@ -729,9 +832,9 @@ def main() -> None:
     beat.phase = "CPU baseline"
     if rank == 0:
         cpu = cpu_mt = None
-        if world == 1 and args.cpu_budget > 0:
+        if args.full and world == 1 and args.cpu_budget > 0:
             cpu = cpu_baseline(args.cpu_budget, args.nx, args.ny, args.depth)
-        if world == 1 and args.cpu_budget_mt > 0:
+        if args.full and world == 1 and args.cpu_budget_mt > 0:
             cpu_mt = cpu_baseline(args.cpu_budget_mt, args.nx, args.ny, args.depth, nthreads=host_threads())
         backend = "RCCL" if args.dist_backend == "nccl" else "gloo"
         if contig:
@@ -765,7 +868,7 @@ def main() -> None:
                 "pixels_per_gpu": npix,
                 "spp_per_gpu": spp_mine,
                 "shard": shard_desc,
-                "live_bounces_per_sample": round(L, 6),
+                "live_bounces_per_sample": None if L is None else round(L, 6),
                 "dist_backend": args.dist_backend if grouped else None,
             },
             "rmse": quality["rmse"] if quality is not None else (
@@ -774,8 +877,8 @@ def main() -> None:
                 parity["bit_exact"] if parity is not None else None),
             "quality": quality,
             "setup": setup,
-            "first_render_ms": round(first_ms, 2) if world == 1 else None,
-            "one_shot": None if world > 1 else {
+            "first_render_ms": round(first_ms, 2) if world == 1 and args.full else None,
+            "one_shot": None if world > 1 or not args.full else {
                 "note": "a fresh process rendering this frame once, like main.cc (its timer, :584-585, 661-663; "
                         "process start, imports and the HIP runtime's first-use initialisation excluded): "
                         "context + scene + jump-table policy + one render (its render through the other kernel "
@@ -787,16 +890,9 @@ def main() -> None:
                 "bench_policy": {"policy": args.ff_tables, "end_to_end_ms": round(e2e_s * 1e3, 1),
                                  "msamples_per_s": round(samples_all / e2e_s / 1e6, 1)},
             },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": round(achieved, 3),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 6),
-                "traffic": traffic,
-                "kernel_ms": round(kernel_ms, 3),
-                "bytes_per_sample_model": round(bytes_per_sample, 3),
-            },
+            "full": args.full,
+            "kernel_ms": round(kernel_ms, 3) if args.steps else None,
+            "roofline": roofline,
             "roofline_valu": valu,
             "cpu_baseline": cpu,
             "cpu_baseline_all_cores": cpu_mt,
@@ -811,7 +907,9 @@ def main() -> None:
                 "kernel": round(one_gpu["kernel_ms"] / kernel_ms_max, 3),
                 "wall": round(one_gpu["wall_ms"] / ms_step, 3),
                 "kernel_ms_max_over_ranks": round(kernel_ms_max, 3)}
-        if samples:
+        if dumped is not None:
+            line["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+        if samples and args.full:
             line["reduced_frame_parity"] = parity if parity is not None else (
                 f"not checked: no committed reduced-frame fixture for {nx}x{ny}, {args.spp} spp, depth "
                 f"{args.depth} at N = {world} (tools/make_golden_reduced.py)")

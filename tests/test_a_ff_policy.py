@@ -83,13 +83,23 @@ def test_policy_auto_direct_stage_follows_measured_allocation():
     assert rec[0][2] == 7_500_000_000 and built[:11] == [0] * 11 and built[11] >= 1
     assert all(r[3] == 300_000_000_000 for r in rec[:11])  # before the chain stage: the fixed count
     chain_at, alloc_ms = rec[11][0], rec[11][4]
-    want = chain_at + int((0.07 + 2.5 * alloc_ms / 1e3) / 1.23e-11)
+    # (never later than the fixed count of a process without chain tables)
+    want = min(300_000_000_000, chain_at + int((0.07 + 2.5 * alloc_ms / 1e3) / 1.23e-11))
     if built[11] == 1:
         assert abs(rec[11][3] - want) <= 1, (rec[11], want)
     reach = next((k for k in range(11, 60) if chain_at + (k - 11) * per >= want), None)
-    if reach is None:
-        pytest.skip(f"the chain tables' allocation took {alloc_ms:.0f} ms: the direct stage is beyond 60 frames")
-    assert built[reach] == 2 and built[reach - 1] < 2, (reach, built)
+    if reach is not None:
+        assert built[reach] == 2 and built[reach - 1] < 2, (reach, built)
+    else:
+        # the chain tables' allocation was slow on this device (the driver
+        # clearing 64 GiB): the break-even lies beyond the 60 frames rendered.
+        # The stage must not come before it: all 60 frames rendered, the
+        # direct block unbuilt, and the break-even count, fixed by the one
+        # measured allocation, the same after every frame.  (That the block is
+        # built on the frame that reaches a count: test_policy_auto_stages.)
+        assert len(rec) == 60 and built[11:] == [1] * 49, (alloc_ms, built)
+        assert all(abs(r[3] - want) <= 1 for r in rec[11:]), (want, [r[3] for r in rec[11:]])
+        assert rec[-1][0] == 60 * per < want
 
 
 def _wait_for_device_memory(timeout_s: float = 60.0) -> None:

@@ -26,7 +26,7 @@ def _run(n, timeout=240):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, "bench.py", "--gpus", str(n), "--dist-backend", "gloo", "--share-gpu", "--workload", "c5",
            "--nx", "96", "--ny", "64", "--spp", "512", "--depth", "20", "--steps", "2", "--warmup", "1",
-           "--ff-tables", "off", "--check"]
+           "--ff-tables", "off", "--check", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

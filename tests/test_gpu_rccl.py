@@ -24,7 +24,7 @@ def test_bench_rccl_reduce_path_on_one_rank():
            "--master-addr", "127.0.0.1", "--master-port", "29655", "bench.py", "--gpus", "1",
            "--force-collective", "--dist-backend", "nccl", "--workload", "c2", "--nx", "64", "--ny", "64",
            "--spp", "8", "--depth", "10", "--steps", "3", "--warmup", "1", "--cpu-budget", "0",
-           "--cpu-budget-mt", "0", "--ff-tables", "off", "--check"]
+           "--cpu-budget-mt", "0", "--ff-tables", "off", "--check", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -47,7 +47,8 @@ def test_bench_rccl_sample_shard_path_on_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", "29657", "bench.py", "--gpus", "1",
            "--force-collective", "--dist-backend", "nccl", "--workload", "c5", "--nx", "96", "--ny", "64",
-           "--spp", "64", "--depth", "20", "--steps", "2", "--warmup", "1", "--ff-tables", "off", "--check"]
+           "--spp", "64", "--depth", "20", "--steps", "2", "--warmup", "1", "--ff-tables", "off", "--check",
+           "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

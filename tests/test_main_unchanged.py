@@ -1,6 +1,6 @@
 """The reference's own main.cc and CornellBox.cpp, compiled UNCHANGED against
-librtp.so (raytracingtherestofyourlife_amd/build.py build_main_unchanged:
-both read from the reference tree, their VTK-m and reference includes
+librtp.so (oracle/ref_build.py through raytracingtherestofyourlife_amd/build.py
+build_main_unchanged, into oracle/_ref/: both read from the reference tree, their VTK-m and reference includes
 resolved by the same-named headers of include/vtkm_compat over
 include/rtp/vtkm_compat.hpp; CornellBox.h and pathtracing/vec3.h are the
 reference's own) -- north_star's "drops into main.cc unchanged" (SURVEY.md
@@ -37,7 +37,7 @@ def main_cc():
     if exe is None:
         exe = build.MAIN_UNCHANGED
         if not os.path.exists(exe):
-            pytest.skip("the reference's main.cc is absent and no prebuilt examples/main_cc exists")
+            pytest.skip("the reference's main.cc is absent and no prebuilt oracle/_ref/main_cc exists")
     return exe
 
 
@@ -57,7 +57,7 @@ def test_main_cc_is_built_from_the_reference_file(main_cc):
 
 def test_reference_cornellbox_equals_the_library_scene(main_cc):
     if not os.path.exists(build.SCENE_CHECK):
-        pytest.skip("tests/cpp/scene_unchanged_check was not built (reference absent)")
+        pytest.skip("oracle/_ref/scene_unchanged_check was not built (reference absent)")
     r = subprocess.run([build.SCENE_CHECK], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     assert r.stdout.strip().splitlines()[-1] == "OK"

@@ -6,7 +6,7 @@
 //   rtp_path [-x 128] [-y 128] [-samplecount 10] [-raydepth 5]
 //            [-hemisphere [-phicount 15] [-thetacount 15]]
 //            [-o output] [-raw prefix] [-variant 0] [-device 0]
-//            [-rank 0 -world 1] [-dry-run]
+//            [-rank 0 -world 1] [-dry-run] [-viewbatch N]
 //
 // Writes <o>.pnm like main.cc, or <o>-<phi>-<theta>.pnm per hemisphere view
 // (generate(), "%.4f" formatting).  -raw additionally dumps the normalised
@@ -14,6 +14,10 @@
 // <raw>-<phi>-<theta>.f32 (hemisphere) for bit-exact comparisons.  -rank/-world shard the hemisphere views (view v
 // goes to rank v mod world; no communication).  -dry-run prints the views
 // (phi, theta, camera position as float bit patterns) and renders nothing.
+// -viewbatch N: the path-traced hemisphere renders its views N at a time, each
+// batch one launch (rtp::runPathViews); default: all of the rank's views,
+// capped so that a batch has at most 2^31-1 pixels and under 1 GiB of output;
+// 0: one launch per view (runPath).  The files are the same bytes either way.
 // -direct: the quad mappers' one-bounce AOVs (main.cc:623-651, generate()
 // :399-420): direct.pnm, depth.pnm, normals.pnm, albedo.pnm (or
 // direct-<phi>-<theta>.pnm ... per hemisphere view), all four from one launch.
@@ -69,7 +73,7 @@ uint32_t bits(float f) {
 
 int main(int argc, char** argv) {
   int x = 128, y = 128, s = 10, depth = 5, variant = 0, device = 0;  // main.cc:56-62 defaults
-  int phiCount = 15, thetaCount = 15, rank = 0, world = 1;
+  int phiCount = 15, thetaCount = 15, rank = 0, world = 1, viewBatch = -1;
   bool hemi = false, dry = false, direct = false;
   std::string out = "output", raw;
   for (int i = 1; i < argc; i++) {
@@ -90,6 +94,7 @@ int main(int argc, char** argv) {
     else if ((v = next("-thetacount"))) thetaCount = std::atoi(v);
     else if ((v = next("-rank"))) rank = std::atoi(v);
     else if ((v = next("-world"))) world = std::atoi(v);
+    else if ((v = next("-viewbatch"))) viewBatch = std::atoi(v);
     else if (!std::strcmp(argv[i], "-hemisphere")) hemi = true;
     else if (!std::strcmp(argv[i], "-dry-run")) dry = true;
     else if (!std::strcmp(argv[i], "-direct")) direct = true;
@@ -116,16 +121,7 @@ int main(int argc, char** argv) {
     rtp::rendering::CanvasRayTracer canvas(x, y);
     rtp::rendering::Camera cam = rtp::DefaultCamera();
     auto dev = std::make_shared<rtp::Device>(device);
-    auto render = [&](const std::string& suffix) {  // generate() / the default branch of main()
-      if (direct) {  // runRay + depth, runNorms, runAlbedo (main.cc:399-420, 625-650)
-        const rtp::rendering::DirectBuffers b = rtp::RunDirect(x, y, cam, cb, dev);
-        rtp::SavePNM("direct" + suffix + ".pnm", b.color, x, y);
-        rtp::SaveDepthPNM("depth" + suffix + ".pnm", b.depth, x, y);
-        rtp::SavePNM("normals" + suffix + ".pnm", b.normals, x, y);
-        rtp::SavePNM("albedo" + suffix + ".pnm", b.albedo, x, y);
-        return;
-      }
-      rtp::runPath(x, y, s, depth, canvas, cam, cb, dev);
+    auto save = [&](const std::string& suffix) {  // the canvas as <o><suffix>.pnm (and the -raw dump)
       rtp::SavePNM(out + suffix + ".pnm", canvas);
       if (!raw.empty()) {
         const std::string fn = suffix.empty() ? raw : raw + suffix + ".f32";
@@ -136,15 +132,50 @@ int main(int argc, char** argv) {
         std::fclose(f);
       }
     };
+    auto render = [&](const std::string& suffix) {  // generate() / the default branch of main()
+      if (direct) {  // runRay + depth, runNorms, runAlbedo (main.cc:399-420, 625-650)
+        const rtp::rendering::DirectBuffers b = rtp::RunDirect(x, y, cam, cb, dev);
+        rtp::SavePNM("direct" + suffix + ".pnm", b.color, x, y);
+        rtp::SaveDepthPNM("depth" + suffix + ".pnm", b.depth, x, y);
+        rtp::SavePNM("normals" + suffix + ".pnm", b.normals, x, y);
+        rtp::SavePNM("albedo" + suffix + ".pnm", b.albedo, x, y);
+        return;
+      }
+      rtp::runPath(x, y, s, depth, canvas, cam, cb, dev);
+      save(suffix);
+    };
+    auto suffix_of = [](const View& w) {
+      char suffix[64];
+      std::snprintf(suffix, sizeof(suffix), "-%.4f-%.4f", w.phi, w.theta);
+      return std::string(suffix);
+    };
     if (hemi) {
       // generateHemisphere's own camera: near plane 1, not main()'s 0.1
       // (main.cc:519 `SetClippingRange(01.f, 5.f)`; it moves the depth AOV)
       cam.SetClippingRange(1.0f, 5.f);
-      for (const View& w : views) {
-        char suffix[64];
-        std::snprintf(suffix, sizeof(suffix), "-%.4f-%.4f", w.phi, w.theta);
-        cam.SetPosition(w.pos);
-        render(suffix);
+      // a batch of views per launch: at most 2^31-1 pixels and under 1 GiB of float4 output
+      const int64_t npv = (int64_t)x * y;
+      const int64_t cap = npv > 0 ? std::max<int64_t>(1, std::min<int64_t>(INT32_MAX / npv, ((1ll << 30) - 1) / (16 * npv))) : 1;
+      const int64_t batch = viewBatch < 0 ? cap : std::min<int64_t>(viewBatch, cap);
+      if (direct || batch == 0) {
+        for (const View& w : views) {
+          cam.SetPosition(w.pos);
+          render(suffix_of(w));
+        }
+      } else {
+        for (size_t b = 0; b < views.size(); b += (size_t)batch) {
+          const size_t e = std::min(views.size(), b + (size_t)batch);
+          std::vector<rtp::rendering::Camera> cams;
+          for (size_t k = b; k < e; k++) {
+            cam.SetPosition(views[k].pos);
+            cams.push_back(cam);
+          }
+          const std::vector<rtp::Vec4f> cols = rtp::runPathViews(x, y, s, depth, cams, cb, dev);
+          for (size_t k = b; k < e; k++) {
+            std::copy(cols.begin() + (k - b) * npv, cols.begin() + (k - b + 1) * npv, canvas.GetColorBuffer().begin());
+            save(suffix_of(views[k]));
+          }
+        }
       }
     } else {
       render("");

@@ -170,6 +170,38 @@ rtp_status rtp_render_pixels(rtp_context* ctx, const rtp_camera* cam, int32_t nx
                              int32_t depth, uint32_t seed_base, const int64_t* pixel_ids, int64_t pixel_count,
                              float* rgba_out, const rtp_pixel_aux* aux, rtp_stats* stats);
 
+/* Many cameras in one launch (main.cc -hemisphere: generateHemisphere renders
+ * one view after the other, each an independent render of the same scene).
+ * A view is a camera and the base of its pixels' seeds (0 for a reference
+ * render; b * nx * ny for the b-th derived-stream sample batch of one
+ * camera, the shard scheme of SURVEY.md 8(e) on one GPU). */
+typedef struct {
+  rtp_camera camera;
+  uint32_t seed_base;
+} rtp_view;
+
+/* views: host array of n_views (read before the call returns).  d_rgba_out:
+ * device float4[n_views*nx*ny], view-major, each view in buffer order.  aux
+ * arrays (nullable): device, n_views*nx*ny.  The result equals n_views calls
+ * of rtp_render_device(views[v].camera, ..., views[v].seed_base, pixel range
+ * [0, nx*ny)) written at offset v*nx*ny, bit for bit (rgb sums, final seeds,
+ * live-bounce counts).  One launch renders all views, the waves' pixel slots
+ * dealt over the view-major entry list; the library runs the per-view loop
+ * itself, with the same outputs, for scenes with a sphere BVH (9 or more
+ * spheres) and when RTP_KERNEL=1, RTP_DEBUG_STATS=1 or RTP_VIEWS_BATCH=0 (the
+ * A/B handle) is set.  Asynchronous like rtp_render_device: the view table is
+ * uploaded in stream order, so calls queued back to back on one stream each
+ * render their own views; stats != NULL synchronises (samples and kernel_ms).
+ * RTP_ERR_INVALID_ARGUMENT, nothing launched: n_views < 1, views NULL, a bad
+ * camera or size, n_views*nx*ny > INT32_MAX (render in batches). */
+rtp_status rtp_render_views_device(rtp_context* ctx, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                                   int32_t spp, int32_t depth, float* d_rgba_out, const rtp_pixel_aux* aux,
+                                   void* hip_stream, rtp_stats* stats);
+/* Host buffers, synchronous (rgba_out: float4[n_views*nx*ny]); stats carries
+ * the totals over all views. */
+rtp_status rtp_render_views(rtp_context* ctx, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                            int32_t spp, int32_t depth, float* rgba_out, rtp_stats* stats);
+
 /* Host-side helpers of the application layer (main.cc). */
 rtp_status rtp_normalize(float* rgba, int64_t n_pixels, int32_t spp);
 rtp_status rtp_write_pnm(const char* path, const float* rgba, int32_t nx, int32_t ny);

@@ -155,6 +155,25 @@ class Device {
   }
   rtp_context* get() const { return ctx_.get(); }
 
+  // rtp_render_views: several cameras of the current scene in one launch.
+  // Returns the UN-normalised colour buffers, view-major (view v at
+  // [v*nx*ny, (v+1)*nx*ny)), each equal to rtp_render of cameras[v] with
+  // seed base seed_bases[v] (empty: all 0).
+  std::vector<Vec4f> RenderViews(const std::vector<rtp_camera>& cameras, int nx, int ny, int samplecount,
+                                 int depthcount, const std::vector<uint32_t>& seed_bases = {},
+                                 rtp_stats* stats = nullptr) const {
+    if (cameras.empty()) throw ErrorBadValue("RenderViews: at least one camera is required");
+    if (!seed_bases.empty() && seed_bases.size() != cameras.size())
+      throw ErrorBadValue("RenderViews: one seed base per camera");
+    if (nx <= 0 || ny <= 0) throw ErrorBadValue("Camera width/height must be greater than zero.");
+    std::vector<rtp_view> views(cameras.size());
+    for (size_t v = 0; v < cameras.size(); v++) views[v] = rtp_view{cameras[v], seed_bases.empty() ? 0u : seed_bases[v]};
+    std::vector<Vec4f> out(cameras.size() * (size_t)nx * (size_t)ny);
+    Check(rtp_render_views(get(), views.data(), (int32_t)views.size(), nx, ny, samplecount, depthcount,
+                           out.data()->data(), stats));
+    return out;
+  }
+
  private:
   std::shared_ptr<rtp_context> ctx_;
 };
@@ -416,6 +435,21 @@ class MapperPathTracer {
     Check(rtp_render(device(), &cam, canvas->GetWidth(), canvas->GetHeight(), samplecount,
                      depthcount, 0u, canvas->GetColorBuffer().data()->data(), &st));
     last_stats = st;
+  }
+
+  // RenderCells for several cameras of one scene in one launch
+  // (Device::RenderViews): the UN-normalised colour buffers of nx x ny
+  // canvases, view-major, view v equal to RenderCells with cameras[v].
+  std::vector<Vec4f> RenderCellsViews(const CellSet& cellset, const CoordinateSystem& coords,
+                                      const std::vector<Camera>& cameras, int nx, int ny) {
+    SetScene(cellset, coords);
+    std::vector<rtp_camera> cams;
+    for (const Camera& c : cameras) cams.push_back(c.ToC());
+    rtp_stats st{};
+    device();
+    std::vector<Vec4f> out = internals_->device->RenderViews(cams, nx, ny, samplecount, depthcount, {}, &st);
+    last_stats = st;
+    return out;
   }
 
   const int samplecount, depthcount;  // as in the reference: (sc, dc)
@@ -700,6 +734,20 @@ inline void runPath(int nx, int ny, int samplecount, int depthcount, rendering::
   rendering::Range sr;
   mapper.RenderCells(cb.ds.GetCellSet(), cb.coord, field, ct, cam, sr);
   Normalize(static_cast<rendering::CanvasRayTracer&>(canvas).GetColorBuffer(), samplecount);
+}
+
+// runPath for every camera of a list in one launch (rtp_render_views): the
+// normalised colour buffers, view-major; view v, at [v*nx*ny, (v+1)*nx*ny),
+// equals runPath's canvas for cams[v].
+inline std::vector<Vec4f> runPathViews(int nx, int ny, int samplecount, int depthcount,
+                                       const std::vector<rendering::Camera>& cams, CornellBox& cb,
+                                       std::shared_ptr<Device> device = nullptr) {
+  rendering::MapperPathTracer mapper(samplecount, depthcount, cb.matIdx, cb.texIdx, cb.matType, cb.texType, cb.tex,
+                                     std::move(device));
+  mapper.SetLights(cb.lightQuad, cb.lightSphere, cb.ior);
+  std::vector<Vec4f> out = mapper.RenderCellsViews(cb.ds.GetCellSet(), cb.coord, cams, nx, ny);
+  Normalize(out, samplecount);
+  return out;
 }
 
 }  // namespace rtp

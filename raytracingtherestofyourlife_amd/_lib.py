@@ -28,6 +28,10 @@ class RtpCamera(ctypes.Structure):
                 ("view_up", ctypes.c_float * 3), ("fov_y_deg", ctypes.c_float)]
 
 
+class RtpView(ctypes.Structure):
+    _fields_ = [("camera", RtpCamera), ("seed_base", ctypes.c_uint32)]
+
+
 class RtpSceneDesc(ctypes.Structure):
     _fields_ = [
         ("points", f32p), ("n_points", ctypes.c_int32),
@@ -75,6 +79,7 @@ EXPORTED_SYMBOLS = [
     "rtp_render_direct", "rtp_render_direct_device", "rtp_sample_color_table", "rtp_quad_scalars",
     "rtp_cornell_point_field", "rtp_write_pnm_depth", "rtp_eval_powf", "rtp_set_ff_tables", "rtp_get_ff_tables",
     "rtp_render_planned_device", "rtp_sphere_walk", "rtp_sphere_walk_oct_mask",
+    "rtp_render_views_device", "rtp_render_views",
 ]
 
 
@@ -149,12 +154,24 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
                                             ctypes.c_int64, vp, vp, ctypes.c_int32, vp, ctypes.POINTER(RtpPixelAux),
                                             vp, ctypes.POINTER(RtpStats)]
+    # An experiment library named by RTP_LIB_PATH may be built from a revision
+    # before the batched views (tools/build_variant.sh RTP_SRC_REV, the A/B
+    # baseline of tools/views_bench.py): it loads without them, and calling
+    # them raises AttributeError.  The in-tree library must export them.
+    older = bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_render_views_device")
+    skip = ("rtp_render_views_device", "rtp_render_views") if older else ()
+    if not older:
+        L.rtp_render_views_device.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp,
+                                              ctypes.POINTER(RtpPixelAux), vp, ctypes.POINTER(RtpStats)]
+        L.rtp_render_views.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_int32, ctypes.c_int32, f32p, ctypes.POINTER(RtpStats)]
     L.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
     L.rtp_get_ff_tables.argtypes = [vp, ctypes.POINTER(RtpFfInfo)]
     L.rtp_sphere_walk.argtypes = [vp]
     L.rtp_sphere_walk_oct_mask.argtypes = [vp]
     for name in EXPORTED_SYMBOLS:
-        if name not in ("rtp_last_error", "rtp_abi_version", "rtp_destroy"):
+        if name not in ("rtp_last_error", "rtp_abi_version", "rtp_destroy") + skip:
             getattr(L, name).restype = ctypes.c_int32
     _lib = L
     return L

@@ -42,6 +42,19 @@ struct rtp_context {
   // buffer a queued kernel may still read.
   hipEvent_t done = nullptr;
   bool pending = false;
+  // View tables of the batched launches (rtp_render_views_device): a pinned
+  // host image and its device copy per slot.  A slot is written by the host
+  // and uploaded in stream order, so it is reused only once `used` (recorded
+  // behind the launch that read it) has completed; calls queued back to back
+  // each take a slot of their own.
+  struct ViewTable {
+    rtp::DevView* host = nullptr;
+    rtp::DevView* dev = nullptr;
+    int32_t capacity = 0;
+    hipEvent_t used = nullptr;
+    bool in_flight = false;
+  };
+  std::vector<ViewTable> view_tables;
   // -direct mode (rtp_direct_host.cpp): reference index of each kept
   // (de-duplicated) quad in DevQuad::orig order, the reference's quad count,
   // the quads' shape bounds, and device scratch for the per-call scalar

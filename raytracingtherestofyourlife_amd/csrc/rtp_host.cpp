@@ -627,6 +627,11 @@ void rtp_destroy(rtp_context* c) {
   if (c->ev1) (void)hipEventDestroy(c->ev1);
   if (c->done) (void)hipEventDestroy(c->done);
   if (c->d_direct) (void)hipFree(c->d_direct);
+  for (rtp_context::ViewTable& t : c->view_tables) {  // (drained above: no launch reads them any more)
+    if (t.host) (void)hipHostFree(t.host);
+    if (t.dev) (void)hipFree(t.dev);
+    if (t.used) (void)hipEventDestroy(t.used);
+  }
   delete c;
 }
 
@@ -1041,13 +1046,16 @@ rtp_status ensure_hist(rtp_context* c, size_t bytes) {
 rtp_status launch(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth,
                   uint32_t seed_base, int64_t pixel_begin, int64_t npix, const int64_t* d_ids, float* d_out,
                   uint32_t* d_seed, uint32_t* d_live, hipStream_t stream, double* kernel_ms,
-                  const int32_t* tile = nullptr, const int32_t* d_wave_begin = nullptr, int plan_waves = 0) {
+                  const int32_t* tile = nullptr, const int32_t* d_wave_begin = nullptr, int plan_waves = 0,
+                  const rtp::DevView* d_views = nullptr) {
   // the kernels index a launch's entries with 32-bit integers
   if (npix > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render: more than 2^31-1 pixels in one launch");
   HIP_TRY(hipSetDevice(c->device));
   rtp::KParams p{};
   if (tile) p.tile_tx = tile[0], p.tile_world = tile[1], p.tile_rank = tile[2];
-  camera_setup(cam, nx, ny, &p.cam);
+  // (batched views: the cameras and seed bases are in the device table, cam is null)
+  if (d_views) p.views = d_views;
+  else camera_setup(cam, nx, ny, &p.cam);
   p.nx = nx, p.ny = ny, p.spp = spp, p.depth = depth;
   p.seed_base = seed_base;
   p.pixel_begin = pixel_begin;
@@ -1294,6 +1302,167 @@ rtp_status rtp_render_tiles_device(rtp_context* c, const rtp_camera* cam, int32_
     stats->kernel_ms = ms;
   }
   return rs;
+}
+
+}  // extern "C"
+
+namespace {
+
+// A free view-table slot of at least n views (rtp_context::ViewTable): one
+// whose last launch has completed, else a new one; past 16 slots the call
+// waits for the queued launches instead of growing further.
+rtp_status acquire_view_table(rtp_context* c, int32_t n, size_t* slot) {
+  auto usable = [&](rtp_context::ViewTable& t) {
+    if (t.in_flight && hipEventQuery(t.used) == hipSuccess) t.in_flight = false;
+    return !t.in_flight;
+  };
+  size_t pick = c->view_tables.size();
+  for (size_t i = 0; i < c->view_tables.size() && pick == c->view_tables.size(); i++)
+    if (usable(c->view_tables[i]) && c->view_tables[i].capacity >= n) pick = i;
+  for (size_t i = 0; i < c->view_tables.size() && pick == c->view_tables.size(); i++)
+    if (usable(c->view_tables[i])) pick = i;  // (too small: reallocated below)
+  if (pick == c->view_tables.size() && c->view_tables.size() >= 16) {
+    rtp_status rs = drain(c);
+    if (rs != RTP_OK) return rs;
+    for (rtp_context::ViewTable& t : c->view_tables) t.in_flight = false;
+    pick = 0;
+    for (size_t i = 1; i < c->view_tables.size(); i++)
+      if (c->view_tables[i].capacity > c->view_tables[pick].capacity) pick = i;
+  }
+  if (pick == c->view_tables.size()) c->view_tables.emplace_back();
+  rtp_context::ViewTable& t = c->view_tables[pick];
+  if (!t.used) HIP_TRY(hipEventCreateWithFlags(&t.used, hipEventDisableTiming));
+  if (t.capacity < n) {
+    if (t.host) (void)hipHostFree(t.host);
+    if (t.dev) (void)hipFree(t.dev);
+    t.host = nullptr, t.dev = nullptr, t.capacity = 0;
+    const int32_t cap = std::max(n, 256);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&t.host), (size_t)cap * sizeof(rtp::DevView), hipHostMallocDefault));
+    HIP_TRY(hipMalloc(&t.dev, (size_t)cap * sizeof(rtp::DevView)));
+    t.capacity = cap;
+  }
+  *slot = pick;
+  return RTP_OK;
+}
+
+// the batched launch unless the scene or the environment asks for the
+// per-view loop (include/rtp.h rtp_render_views_device)
+bool views_batched(const rtp_context* c) {
+  auto is = [](const char* name, char v) {
+    const char* e = getenv(name);
+    return e && e[0] == v;
+  };
+  return !c->use_bvh && !is("RTP_KERNEL", '1') && !is("RTP_DEBUG_STATS", '1') && !is("RTP_VIEWS_BATCH", '0');
+}
+
+rtp_status check_views_args(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                            int32_t spp, int32_t depth) {
+  if (!c || !views) return fail(RTP_ERR_INVALID_ARGUMENT, "render_views: NULL argument");
+  if (n_views < 1) return fail(RTP_ERR_INVALID_ARGUMENT, "render_views: n_views must be >= 1");
+  for (int32_t v = 0; v < n_views; v++) {
+    rtp_status rs = check_render_args(c, &views[v].camera, nx, ny, spp, depth);
+    if (rs != RTP_OK) return rs;
+  }
+  // (entries are 32-bit in the kernel)
+  if ((int64_t)n_views * nx * ny > INT32_MAX)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "render_views: n_views * nx * ny exceeds 2^31-1 entries; render in batches");
+  return RTP_OK;
+}
+
+// rtp_render_views_device behind its argument checks
+rtp_status render_views_device(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                               int32_t spp, int32_t depth, float* d_out, uint32_t* d_seed, uint32_t* d_live,
+                               hipStream_t stream, double* kernel_ms) {
+  const int64_t N = (int64_t)nx * ny;
+  if (!views_batched(c)) {  // the per-view loop: one rtp_render_device each, at offset v * N
+    double total = 0;
+    for (int32_t v = 0; v < n_views; v++) {
+      double ms = 0;
+      rtp_status rs = launch(c, &views[v].camera, nx, ny, spp, depth, views[v].seed_base, 0, N, nullptr,
+                             d_out + 4 * N * v, d_seed ? d_seed + N * v : nullptr, d_live ? d_live + N * v : nullptr,
+                             stream, kernel_ms ? &ms : nullptr);
+      if (rs != RTP_OK) return rs;
+      total += ms;
+    }
+    if (kernel_ms) *kernel_ms = total;
+    return RTP_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  size_t slot = 0;
+  rtp_status rs = acquire_view_table(c, n_views, &slot);
+  if (rs != RTP_OK) return rs;
+  rtp::DevView* const host = c->view_tables[slot].host;
+  rtp::DevView* const dev = c->view_tables[slot].dev;
+  for (int32_t v = 0; v < n_views; v++) {
+    host[v] = rtp::DevView{};
+    camera_setup(&views[v].camera, nx, ny, &host[v].cam);  // the host code of a single render
+    host[v].seed_base = views[v].seed_base;
+  }
+  HIP_TRY(hipMemcpyAsync(dev, host, (size_t)n_views * sizeof(rtp::DevView), hipMemcpyHostToDevice, stream));
+  c->view_tables[slot].in_flight = true;  // (from the upload on: the event below closes the slot's use)
+  rs = launch(c, nullptr, nx, ny, spp, depth, 0u, 0, N * n_views, nullptr, d_out, d_seed, d_live, stream, kernel_ms,
+              nullptr, nullptr, 0, dev);
+  HIP_TRY(hipEventRecord(c->view_tables[slot].used, stream));
+  return rs;
+}
+
+}  // namespace
+
+extern "C" {
+
+// n_views cameras in one launch (include/rtp.h): the pool kernel's kViews
+// instances over the view-major entry list, or the per-view loop.
+rtp_status rtp_render_views_device(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                                   int32_t spp, int32_t depth, float* d_rgba_out, const rtp_pixel_aux* aux,
+                                   void* hip_stream, rtp_stats* stats) {
+  rtp_status rs = check_views_args(c, views, n_views, nx, ny, spp, depth);
+  if (rs != RTP_OK) return rs;
+  if (!d_rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_views_device: bad output");
+  double ms = 0;
+  rs = render_views_device(c, views, n_views, nx, ny, spp, depth, d_rgba_out, aux ? aux->final_seed : nullptr,
+                           aux ? aux->live_bounces : nullptr, (hipStream_t)hip_stream, stats ? &ms : nullptr);
+  if (rs == RTP_OK && stats) {
+    *stats = rtp_stats{};
+    stats->samples = (uint64_t)n_views * (uint64_t)nx * (uint64_t)ny * (uint64_t)spp;
+    stats->kernel_ms = ms;
+  }
+  return rs;
+}
+
+rtp_status rtp_render_views(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
+                            int32_t spp, int32_t depth, float* rgba_out, rtp_stats* stats) {
+  rtp_status rs = check_views_args(c, views, n_views, nx, ny, spp, depth);
+  if (rs != RTP_OK) return rs;
+  if (!rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_views: rgba_out is NULL");
+  HIP_TRY(hipSetDevice(c->device));
+  const int64_t n = (int64_t)n_views * nx * ny;
+  float* d_out = nullptr;
+  uint32_t* d_live = nullptr;
+  hipError_t e = hipMalloc(&d_out, (size_t)n * 16);
+  if (e == hipSuccess) e = hipMalloc(&d_live, (size_t)n * 4);
+  std::vector<uint32_t> live((size_t)n);
+  double ms = 0;
+  if (e != hipSuccess) rs = hip_fail(e, "render_views: device buffers");
+  if (rs == RTP_OK) rs = render_views_device(c, views, n_views, nx, ny, spp, depth, d_out, nullptr, d_live, nullptr, &ms);
+  if (rs == RTP_OK) {
+    e = hipMemcpy(rgba_out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rs = hip_fail(e, "render_views: copy back");
+  }
+  if (d_out) (void)hipFree(d_out);
+  if (d_live) (void)hipFree(d_live);
+  if (rs != RTP_OK) return rs;
+  if (stats) {
+    *stats = rtp_stats{};
+    stats->samples = (uint64_t)n * (uint64_t)spp;
+    for (int64_t i = 0; i < n; i++) {
+      stats->live_bounces += live[i];
+      const float* px = rgba_out + 4 * i;
+      stats->nan_pixels += (std::isnan(px[0]) || std::isnan(px[1]) || std::isnan(px[2])) ? 1 : 0;
+    }
+    stats->kernel_ms = ms;
+  }
+  return RTP_OK;
 }
 
 // Diagnostics: sums of the pool kernel's per-wave counters from the last launch

@@ -812,6 +812,53 @@ RTP_DEV void pixel_xy(const KP& p, int k, int& pi, int& pj) {
     }
   }
 }
+// kViews (batched views, KParams::views): entry k of the view-major list ->
+// its view v = k / (nx*ny) and the pixel u = k % (nx*ny) inside it.  The same
+// shape as above: a float reciprocal quotient with one correction each way
+// while the launch has at most 2^22 entries, else integer division (a
+// wave-uniform branch).  With k < 2^22 the product k * rcp(npv) carries a
+// relative error below 1.5 * 2^-23 (v_rcp_f32: 1 ulp, the product's rounding:
+// half an ulp; k and npv are exact floats), so the estimate is within
+// 0.75 / npv < 1 of the real quotient for every npv >= 1 and its floor is off
+// by at most one.  (At the other modes' 2^24 bound the error reaches 1 for
+// npv = 3.)  Exact for every k < 2^31: (q + 1) * npv <= k + 2 * npv stays
+// inside 32 bits on the float path, and the fallback divides integers.
+template <class KP>
+RTP_DEV void view_split(const KP& p, int k, int& v, int& u) {
+  const int npv = p.nx * p.ny;  // (<= npix <= INT32_MAX: the host checks)
+  if (p.npix <= (int64_t)1 << 22) {
+    int q = (int)((float)k * __builtin_amdgcn_rcpf((float)npv));
+    q += (q + 1) * npv <= k;
+    q -= q * npv > k;
+    v = q;
+  } else {
+    v = (int)((uint32_t)k / (uint32_t)npv);
+  }
+  u = k - v * npv;
+}
+// the pixel's column and row inside its view (pixel_xy's split of u)
+template <class KP>
+RTP_DEV void view_pixel_xy(const KP& p, int u, int& pi, int& pj) {
+  const int nx = p.nx;
+  if ((int64_t)nx * p.ny <= (int64_t)1 << 24) {
+    int q = (int)((float)u * __builtin_amdgcn_rcpf((float)nx));
+    q += (q + 1) * nx <= u;
+    q -= q * nx > u;
+    pj = q;
+  } else {
+    pj = (int)((uint32_t)u / (uint32_t)nx);
+  }
+  pi = u - pj * nx;
+}
+// the first seed of entry k: views[v].seed_base + u (each view an independent
+// reference render, seeds[i] = i: MapperPathTracer.cxx:265-267)
+template <class KP>
+RTP_DEV uint32_t view_seed(const KP& p, int k) {
+  int v, u;
+  view_split(p, k, v, u);
+  return p.views[v].seed_base + (uint32_t)u;
+}
+
 // kTiles: a separate kernel instance (rtp_render_tiles_device).  A runtime
 // branch here changed the compiler's code for the whole scheduling loop of
 // the other modes (+9% time), as other additions to the refill path did.
@@ -955,7 +1002,13 @@ typedef const __attribute__((address_space(1))) uint32_t GU32;
 // all its samples writes the pixel out and claims the next unclaimed entry
 // (one atomic per batch), so no wave idles while entries remain, instead of
 // waves of 128 pixels each running in generations with a tail per wave.
-template <bool kStats, bool kBvh, bool kTiles, bool kPlan, int kWPB, bool kLdsBvh, bool kSteal = false>
+// kViews: a batched launch over several cameras (KParams::views, view_split
+// above): the entries of different views share a wave under the interleaved
+// deal and under stealing, so the camera is per lane -- each refill gathers
+// its view's DevCamera from the global table (three 16-byte loads; the table
+// of a hemisphere sweep is ~14 KB and stays in the vector L1 / L2).
+template <bool kStats, bool kBvh, bool kTiles, bool kPlan, int kWPB, bool kLdsBvh, bool kSteal = false,
+          bool kViews = false>
 __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const KParams& p, int n_waves,
                                           unsigned char* smem, float* s_qshade, uint32_t* s_bvh,
                                           uint32_t* s_entry_all = nullptr) {
@@ -1001,7 +1054,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
   for (int j = lane; j < n_slots; j += 64) {
     const int64_t k = kPlan ? (int64_t)(wbase + j) : (int64_t)j * n_waves + w;
     if constexpr (kSteal) s_entry[j] = (uint32_t)k;
-    s_seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
+    if constexpr (kViews) s_seed[j] = view_seed(p, (int)k);
+    else s_seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
     s_r[j] = 0.f;
     s_g[j] = 0.f;
     s_b[j] = 0.f;
@@ -1213,7 +1267,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
             const unsigned long long kn = base + lane_rank(done);
             if (kn < (unsigned long long)p.npix) {  // a fresh pixel in this slot, at the front of READY below
               s_entry[fslot] = (uint32_t)kn;
-              s_seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
+              if constexpr (kViews) s_seed[fslot] = view_seed(p, (int)kn);
+              else s_seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
               s_r[fslot] = 0.f;
               s_g[fslot] = 0.f;
               s_b[fslot] = 0.f;
@@ -1269,10 +1324,19 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
         // segment pointer: &p would copy p to scratch)
         CKP& P = kparams();
         int pi, pj;
-        pixel_xy<kTiles>(P, kSteal ? (int)s_entry[slot] : kPlan ? wbase + slot : slot * n_waves + w, pi,
-                         pj);  // (32-bit index: a 64-bit one spilled)
-        ps.dir = camera_ray(P.cam, pi, pj, P.nx, P.ny, seed);
-        ps.org = ld3(P.cam.eye);
+        if constexpr (kViews) {  // the entry's view: its camera gathered per lane
+          int v, u;
+          view_split(P, kSteal ? (int)s_entry[slot] : slot * n_waves + w, v, u);
+          view_pixel_xy(P, u, pi, pj);
+          const DevCamera vc = P.views[v].cam;
+          ps.dir = camera_ray(vc, pi, pj, P.nx, P.ny, seed);
+          ps.org = ld3(vc.eye);
+        } else {
+          pixel_xy<kTiles>(P, kSteal ? (int)s_entry[slot] : kPlan ? wbase + slot : slot * n_waves + w, pi,
+                           pj);  // (32-bit index: a 64-bit one spilled)
+          ps.dir = camera_ray(P.cam, pi, pj, P.nx, P.ny, seed);
+          ps.org = ld3(P.cam.eye);
+        }
         ps.d = 0;
         ps.nonfinite = false;
         has_path = true;
@@ -1433,17 +1497,19 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
 #else
 #define RTP_POOL_VGPR_ATTR
 #endif
-template <bool kStats, bool kBvh, bool kTiles = false, bool kPlan = false, bool kSteal = false>
+template <bool kStats, bool kBvh, bool kTiles = false, bool kPlan = false, bool kSteal = false, bool kViews = false>
 __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_ATTR
     rtp_render_pool(const DevScene* __restrict__ sc, KParams p, int n_waves) {
+  static_assert(!kViews || (!kStats && !kBvh && !kTiles && !kPlan), "batched views: the plain and stealing instances");
   __shared__ __align__(16) unsigned char smem[kPoolLdsBytes];
   __shared__ __align__(16) float s_qshade[kQTableFloats];
   if constexpr (kSteal) {
     __shared__ uint32_t s_entry[kWavesPerBlock * kPool];
-    pool_body<kStats, kBvh, kTiles, kPlan, kWavesPerBlock, false, true>(sc, p, n_waves, smem, s_qshade, nullptr,
-                                                                        s_entry);
+    pool_body<kStats, kBvh, kTiles, kPlan, kWavesPerBlock, false, true, kViews>(sc, p, n_waves, smem, s_qshade,
+                                                                                nullptr, s_entry);
   } else {
-    pool_body<kStats, kBvh, kTiles, kPlan, kWavesPerBlock, false>(sc, p, n_waves, smem, s_qshade, nullptr);
+    pool_body<kStats, kBvh, kTiles, kPlan, kWavesPerBlock, false, false, kViews>(sc, p, n_waves, smem, s_qshade,
+                                                                                 nullptr);
   }
 }
 
@@ -1750,7 +1816,7 @@ extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const 
 extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves,
                                         int bvh, hipStream_t stream, int lds_bytes) {
   if (p->npix <= 0) return hipSuccess;
-  if (variant == 1 && p->tile_world > 0) return hipErrorNotSupported;  // (v1 takes pixel lists or ranges)
+  if (variant == 1 && (p->tile_world > 0 || p->views)) return hipErrorNotSupported;  // (v1 takes pixel lists or ranges)
   if (variant == 1) {
     const int64_t grid = (p->npix + 255) / 256;
     if (bvh)
@@ -1758,7 +1824,7 @@ extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::K
     else
       hipLaunchKernelGGL(rtp::rtp_render_lockstep<false>, dim3((unsigned)grid), dim3(256), 0, stream, scene, *p);
   } else if (bvh == 2) {  // the sphere BVH walked out of LDS
-    if (p->wave_begin || lds_bytes <= 0 || lds_bytes > rtp::kLdsWalkDynBytes) return hipErrorNotSupported;
+    if (p->wave_begin || p->views || lds_bytes <= 0 || lds_bytes > rtp::kLdsWalkDynBytes) return hipErrorNotSupported;
     (void)lds_bvh_resident_blocks_per_cu();  // (sets the kernels' dynamic-LDS limit once)
     const int blocks = (waves + rtp::kLdsBvhWavesPerBlock - 1) / rtp::kLdsBvhWavesPerBlock;
     const dim3 g((unsigned)blocks), b(64 * rtp::kLdsBvhWavesPerBlock);
@@ -1773,7 +1839,13 @@ extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::K
     const char* st = getenv("RTP_DEBUG_STATS");
     const bool stats = p->dbg && st && st[0] == '1';
     const dim3 g((unsigned)blocks), b(256);
-    if (p->wave_begin) {  // a planned launch (pixel list or range, no BVH)
+    if (p->views) {  // batched views: their own instances (no sphere BVH, stats, plan or tile deal)
+      if (bvh || stats || p->wave_begin || p->tile_world > 0 || p->pixel_ids) return hipErrorNotSupported;
+      if ((int64_t)waves * rtp::kPool < p->npix)  // work stealing (rtp_plan_steal)
+        hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, false, true, true>), g, b, 0, stream, scene, *p, waves);
+      else
+        hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, false, false, true>), g, b, 0, stream, scene, *p, waves);
+    } else if (p->wave_begin) {  // a planned launch (pixel list or range, no BVH)
       if (bvh || p->tile_world > 0) return hipErrorNotSupported;
       if (stats) hipLaunchKernelGGL((rtp::rtp_render_pool<true, false, false, true>), g, b, 0, stream, scene, *p, waves);
       else hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, true>), g, b, 0, stream, scene, *p, waves);

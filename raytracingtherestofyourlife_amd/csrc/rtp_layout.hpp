@@ -239,6 +239,16 @@ struct DevCamera {
   float eye[3], nlook[3], dx[3], dy[3];
 };
 
+// One view of a batched launch (pool kernel kViews, rtp_render_views_device):
+// its camera constants and the base of its pixels' seeds.  64 bytes: a lane
+// gathers its view's camera as three 16-byte loads, the seed base as one word.
+struct alignas(16) DevView {
+  DevCamera cam;
+  uint32_t seed_base;
+  uint32_t pad[3];
+};
+static_assert(sizeof(DevView) == 64 && offsetof(DevView, seed_base) == 48, "DevView: 3 x 16 B of camera + seed word");
+
 constexpr int kFfTables = 6;  // jump tables for 32, 16, 8, 4, 2, 1 dead depths (default 4 built)
 constexpr int kFfMaxSteps = 64;  // build kernel: tables for 1..63 dead depths
 // the fused table build's outputs: t[r] receives the state after r dead
@@ -274,6 +284,10 @@ struct KParams {
   int32_t ffd_first, ffd_count;
   // planned launch (nullable): wave w owns entries [wave_begin[w], wave_begin[w+1])
   const int32_t* wave_begin;
+  // batched views (nullable; pool kernel kViews): entry k is pixel k % (nx*ny)
+  // of view k / (nx*ny), view-major; npix = n_views * nx * ny; cam, seed_base,
+  // pixel_begin, pixel_ids and the tile deal are unused
+  const DevView* views;
 };
 
 // -direct mode (main.cc:120-251): one launch renders the requested AOVs of

@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import RtpCamera, RtpFfInfo, RtpPixelAux, RtpSceneDesc, RtpStats, check
+from ._lib import RtpCamera, RtpFfInfo, RtpPixelAux, RtpSceneDesc, RtpStats, RtpView, check
 
 
 class ErrorBadValue(ValueError):
@@ -340,6 +340,48 @@ class Device:
                                               ctypes.byref(st) if timed else None))
         return st
 
+    @staticmethod
+    def _views(cameras, seed_bases):
+        """The rtp_view array of a camera list (checked before the library is touched)."""
+        cameras = list(cameras)
+        if not cameras:
+            raise ErrorBadValue("render_views: at least one camera is required")
+        if seed_bases is None:
+            seed_bases = [0] * len(cameras)
+        seed_bases = [int(b) for b in seed_bases]
+        if len(seed_bases) != len(cameras):
+            raise ErrorBadValue(f"render_views: {len(seed_bases)} seed bases for {len(cameras)} cameras")
+        views = (RtpView * len(cameras))()
+        for v, (cam, base) in enumerate(zip(cameras, seed_bases)):
+            views[v].camera = cam.to_c()
+            views[v].seed_base = base & 0xFFFFFFFF
+        return views
+
+    def render_views(self, cameras, nx: int, ny: int, spp: int, depth: int, seed_bases=None):
+        """Several cameras in one launch into host memory (rtp_render_views):
+        (rgba_sum[V, nx*ny, 4], stats with the totals over all views).  View v
+        equals render(cameras[v], ..., seed_base=seed_bases[v]) bit for bit."""
+        views = self._views(cameras, seed_bases)
+        out = np.zeros((len(views), nx * ny, 4), dtype=np.float32)
+        st = RtpStats()
+        check(self._L.rtp_render_views(self.handle, views, len(views), nx, ny, spp, depth,
+                                       out.ctypes.data_as(_lib.f32p), ctypes.byref(st)))
+        return out, st
+
+    def render_views_device(self, cameras, nx: int, ny: int, spp: int, depth: int, out_ptr: int, seed_bases=None,
+                            stream: int = 0, seed_ptr: int = 0, live_ptr: int = 0, timed: bool = False):
+        """Device-resident rtp_render_views_device (out_ptr: device
+        float4[V * nx*ny], view-major; seed_ptr / live_ptr: device u32 arrays
+        of the same length).  Asynchronous unless timed."""
+        views = self._views(cameras, seed_bases)
+        aux = RtpPixelAux(ctypes.cast(seed_ptr, _lib.u32p) if seed_ptr else None,
+                          ctypes.cast(live_ptr, _lib.u32p) if live_ptr else None)
+        st = RtpStats()
+        check(self._L.rtp_render_views_device(self.handle, views, len(views), nx, ny, spp, depth,
+                                              ctypes.c_void_p(out_ptr), ctypes.byref(aux),
+                                              ctypes.c_void_p(stream or None), ctypes.byref(st) if timed else None))
+        return st
+
     FF_POLICIES = {"auto": _lib.RTP_FF_TABLES_AUTO, "off": _lib.RTP_FF_TABLES_OFF, "on": _lib.RTP_FF_TABLES_ON}
 
     def sphere_walk(self) -> str:
@@ -507,3 +549,64 @@ def runPath(nx: int, ny: int, samplecount: int, depthcount: int, canvas: CanvasR
                        cb.ior)
     normalize(canvas.GetColorBuffer(), samplecount)
     return mapper
+
+
+def runPathViews(nx: int, ny: int, samplecount: int, depthcount: int, cameras, cb: CornellBox,
+                 device: int | Device = 0) -> np.ndarray:
+    """runPath (main.cc:289-323) for every camera of a list in one launch:
+    the normalised colour buffers [V, nx*ny, 4], view v equal to runPath's
+    canvas for cameras[v]."""
+    cameras = list(cameras)
+    if not cameras:
+        raise ErrorBadValue("runPathViews: at least one camera is required")
+    dev = device if isinstance(device, Device) else Device(device)
+    cellset = cb.ds.GetCellSet()
+    dev.set_scene(cb.coord, cellset.quad_points, cb.matIdx[0], cb.texIdx[0], cellset.sphere_points, cb.SphereRadii,
+                  cb.matIdx[1], cb.texIdx[1], cb.matType, cb.texType, cb.tex, cb.light_quad_points,
+                  cb.light_sphere_point, cb.ior)
+    out, _ = dev.render_views(cameras, nx, ny, samplecount, depthcount)
+    normalize(out.reshape(-1, 4), samplecount)
+    return out
+
+
+def hemisphere_cameras(phi_count: int = 15, theta_count: int = 15) -> list:
+    """The cameras of generateHemisphere (main.cc:504-561) with the parameters
+    main() passes (:583-595), in its loop order: phi in [0, 1) by 1/phiCount,
+    theta in [0, 2pi) by (float)(2pi)/thetaCount, radius -1078/555 around
+    (278,278,278)/555.  The reference's float variables and its mix of float
+    and double operations, restated in float32 (cosf/sinf are libm's, as in
+    the C++ driver); each camera also carries its .phi and .theta (the view's
+    file-name suffix is "-%.4f-%.4f" of them)."""
+    if phi_count < 1 or theta_count < 1:
+        raise ErrorBadValue("hemisphere_cameras: phi_count and theta_count must be >= 1")
+    import ctypes.util
+
+    libm = ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6")
+    f32 = np.float32
+    fn = {}
+    for name in ("cosf", "sinf"):
+        f = getattr(libm, name)
+        f.argtypes, f.restype = [ctypes.c_float], ctypes.c_float
+        fn[name] = lambda x, f=f: f32(f(float(x)))
+    theta_end = f32(2 * 3.14159265358979323846)
+    r_theta = f32(theta_end / f32(theta_count))
+    r_phi = f32(f32(1.0) / f32(phi_count))
+    r = f32(-1078 / 555.0)
+    c = 278 / 555.0
+    phi_bound = 1.0 - 0.5 * float(r_phi)  # compared in double
+    cams = []
+    phi = f32(0.0)
+    while float(phi) < phi_bound:
+        theta = f32(0.0)
+        while theta < theta_end:
+            px = f32(f32(r * fn["cosf"](theta)) * fn["sinf"](phi))
+            py = f32(f32(r * fn["sinf"](theta)) * fn["sinf"](phi))
+            pz = f32(r * fn["cosf"](phi))
+            cam = default_camera()
+            cam.SetClippingRange(1.0, 5.0)  # generateHemisphere's own near plane (main.cc:519)
+            cam.SetPosition([f32(float(px) + c), f32(float(py) + c), f32(float(pz) + c)])
+            cam.phi, cam.theta = float(phi), float(theta)
+            cams.append(cam)
+            theta = f32(theta + r_theta)
+        phi = f32(phi + r_phi)
+    return cams

@@ -1,0 +1,280 @@
+"""Many cameras in one launch (rtp_render_views_device; rtp_kernels.hip
+pool_body kViews): the entries of a view-major list over all views are dealt
+over the resident waves, each entry with its own view's camera and seed base.
+Every view must equal its own rtp_render_device call bit for bit -- rgb sums,
+final RNG states, live-bounce counts -- and the oracle's render of that
+camera."""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from _util import assert_render_equal, same_bits_or_both_nan
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _plan_steal(npix: int, bvh: int = 0) -> int:
+    from raytracingtherestofyourlife_amd import _lib
+
+    L = _lib.load()
+    L.rtp_plan_steal.restype = ctypes.c_int
+    L.rtp_plan_steal.argtypes = [ctypes.c_int64, ctypes.c_int]
+    return L.rtp_plan_steal(npix, bvh)
+
+
+def _hemi(phi_count, theta_count, keep=None):
+    import raytracingtherestofyourlife_amd as rtp
+
+    cams = rtp.hemisphere_cameras(phi_count, theta_count)
+    return cams if keep is None else [cams[i] for i in keep]
+
+
+def _views_device(device, cams, nx, ny, spp, depth, seed_bases=None, env=None, monkeypatch=None, fill=3.0):
+    """One render_views_device call: device tensors (rgba [V*N, 4], seeds, live)."""
+    import torch
+
+    for k, v in (env or {}).items():
+        monkeypatch.setenv(k, v)
+    n = len(cams) * nx * ny
+    out = torch.full((n, 4), fill, dtype=torch.float32, device="cuda")
+    seeds = torch.zeros(n, dtype=torch.int32, device="cuda")
+    live = torch.zeros(n, dtype=torch.int32, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    device.render_views_device(cams, nx, ny, spp, depth, out.data_ptr(), seed_bases=seed_bases, stream=s,
+                               seed_ptr=seeds.data_ptr(), live_ptr=live.data_ptr())
+    torch.cuda.synchronize()
+    for k in env or {}:
+        monkeypatch.delenv(k)
+    return out, seeds, live
+
+
+def _host(t):
+    out, seeds, live = t
+    return out.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), live.cpu().numpy().view(np.uint32)
+
+
+def _single_device(device, cam, nx, ny, spp, depth, seed_base=0):
+    """The contract's right-hand side: rtp_render_device of one camera."""
+    import torch
+
+    n = nx * ny
+    out = torch.full((n, 4), 7.0, dtype=torch.float32, device="cuda")
+    seeds = torch.zeros(n, dtype=torch.int32, device="cuda")
+    live = torch.zeros(n, dtype=torch.int32, device="cuda")
+    device.render_device(cam, nx, ny, spp, depth, out.data_ptr(), seed_base=seed_base,
+                         stream=torch.cuda.current_stream().cuda_stream, seed_ptr=seeds.data_ptr(),
+                         live_ptr=live.data_ptr())
+    torch.cuda.synchronize()
+    return _host((out, seeds, live))
+
+
+def _oracle_cam(oracle, nx, ny, cam):
+    return oracle.camera_setup(nx, ny, position=cam.position, look_at=cam.look_at, view_up=cam.view_up,
+                               fov_y=float(cam.fov))
+
+
+def test_views_equal_loop_and_oracle(device, oracle, monkeypatch):
+    """The non-stealing instance: 5 views of 48 x 40 (1920 pixels a view, not
+    a multiple of 64), four hemisphere positions and one camera with its own
+    look-at, up vector and field of view; batched == the per-view loop == the
+    oracle on every pixel of every view."""
+    import raytracingtherestofyourlife_amd as rtp
+
+    nx, ny, spp, depth = 48, 40, 7, 6
+    cams = _hemi(3, 4, keep=[5, 6, 9, 11])
+    own = rtp.Camera()
+    own.SetPosition([0.9, 0.7, -1.1])
+    own.SetLookAt([0.4, 0.45, 0.55])
+    own.SetViewUp([0.1, 1.0, 0.05])
+    own.SetFieldOfView(52.0)
+    cams.insert(2, own)
+    n = nx * ny
+    assert _plan_steal(len(cams) * n) == 0
+    device.set_cornell_box(0)
+    batched = _host(_views_device(device, cams, nx, ny, spp, depth))
+    loop = _host(_views_device(device, cams, nx, ny, spp, depth, env={"RTP_VIEWS_BATCH": "0"}, monkeypatch=monkeypatch))
+    assert_render_equal(batched, loop, "batched vs the per-view loop")
+    sc = oracle.cornell_box(0)
+    pix = np.arange(n, dtype=np.int64)
+    for v, cam in enumerate(cams):
+        want = oracle.render_pixels(sc, _oracle_cam(oracle, nx, ny, cam), nx, ny, spp, depth, pix)
+        for name, got in (("batched", batched), ("loop", loop)):
+            assert_render_equal(tuple(a[v * n:(v + 1) * n] for a in got), want, f"{name} view {v} vs the oracle")
+
+
+def test_views_stealing(device, oracle, monkeypatch):
+    """The stealing instance: 40 hemisphere views of 256 x 208 (2.13 M
+    entries); batched == loop everywhere, == the oracle on the first and last
+    entries, both sides of every view boundary and a random sample."""
+    nx, ny, spp, depth = 256, 208, 2, 50
+    cams = _hemi(8, 5)
+    n = nx * ny
+    total = len(cams) * n
+    assert len(cams) == 40 and _plan_steal(total) > 0, "the launch must be large enough to steal"
+    device.set_cornell_box(0)
+    batched = _host(_views_device(device, cams, nx, ny, spp, depth))
+    loop = _host(_views_device(device, cams, nx, ny, spp, depth, env={"RTP_VIEWS_BATCH": "0"}, monkeypatch=monkeypatch))
+    assert_render_equal(batched, loop, "stolen batch vs the per-view loop")
+    edges = np.concatenate([[v * n - 1, v * n] for v in range(1, len(cams))])
+    entries = np.unique(np.r_[np.arange(32), np.arange(total - 64, total), edges,
+                              np.random.default_rng(5).choice(total, 126, replace=False)]).astype(np.int64)
+    sc = oracle.cornell_box(0)
+    for v in np.unique(entries // n):
+        e = entries[entries // n == v]
+        want = oracle.render_pixels(sc, _oracle_cam(oracle, nx, ny, cams[v]), nx, ny, spp, depth, e - v * n)
+        assert_render_equal(tuple(a[e] for a in batched), want, f"stolen batch view {v} vs the oracle")
+
+
+def test_views_index_past_2_24(device, monkeypatch):
+    """2 views of 4100 x 4099: 16 805 900 pixels a view (> 2^24) and 33.6 M
+    entries, so both index splits take their integer path; compared with the
+    per-view loop on the device."""
+    import torch
+
+    nx, ny, spp, depth = 4100, 4099, 1, 3
+    assert nx * ny > 1 << 24
+    cams = _hemi(2, 2, keep=[2, 3])
+    device.set_cornell_box(0)
+    a = _views_device(device, cams, nx, ny, spp, depth)
+    b = _views_device(device, cams, nx, ny, spp, depth, env={"RTP_VIEWS_BATCH": "0"}, monkeypatch=monkeypatch)
+    ra, rb = a[0][:, :3], b[0][:, :3]
+    same = (ra.contiguous().view(torch.int32) == rb.contiguous().view(torch.int32)) | (torch.isnan(ra) & torch.isnan(rb))
+    assert bool(same.all()), f"{int((~same).sum())} rgb values differ"
+    assert torch.equal(a[1], b[1]), "final RNG states differ"
+    assert torch.equal(a[2], b[2]), "live-bounce counts differ"
+    assert int(a[2].min()) >= 1  # (every entry was rendered: a sample has at least one live bounce)
+
+
+def test_views_seed_base_per_view(device):
+    """One camera four times with seed_base = b * nx * ny: the derived-stream
+    sample batches of a single frame, each equal to render_device's."""
+    import raytracingtherestofyourlife_amd as rtp
+
+    nx, ny, spp, depth = 40, 24, 5, 8
+    n = nx * ny
+    cam = rtp.default_camera()
+    bases = [b * n for b in range(4)]
+    device.set_cornell_box(0)
+    got = _host(_views_device(device, [cam] * 4, nx, ny, spp, depth, seed_bases=bases))
+    for b, base in enumerate(bases):
+        want = _single_device(device, cam, nx, ny, spp, depth, seed_base=base)
+        assert_render_equal(tuple(a[b * n:(b + 1) * n] for a in got), want, f"seed base {base}")
+    assert not np.array_equal(got[1][:n], got[1][n:2 * n])
+
+
+def test_views_back_to_back_async(device, monkeypatch):
+    """Two calls with different tables and view counts queued on one stream
+    with no synchronise between them: each renders its own table."""
+    import torch
+
+    nx, ny, spp, depth = 32, 24, 3, 6
+    n = nx * ny
+    first, second = _hemi(3, 4, keep=[4, 7, 10]), _hemi(3, 4, keep=[11, 5, 8, 6, 9])
+    device.set_cornell_box(0)
+    s = torch.cuda.current_stream().cuda_stream
+    bufs = []
+    for cams in (first, second):
+        out = torch.full((len(cams) * n, 4), 3.0, dtype=torch.float32, device="cuda")
+        seeds = torch.zeros(len(cams) * n, dtype=torch.int32, device="cuda")
+        live = torch.zeros(len(cams) * n, dtype=torch.int32, device="cuda")
+        device.render_views_device(cams, nx, ny, spp, depth, out.data_ptr(), stream=s, seed_ptr=seeds.data_ptr(),
+                                   live_ptr=live.data_ptr())
+        bufs.append((out, seeds, live))
+    torch.cuda.synchronize()
+    for cams, got in zip((first, second), bufs):
+        want = _host(_views_device(device, cams, nx, ny, spp, depth, env={"RTP_VIEWS_BATCH": "0"},
+                                   monkeypatch=monkeypatch))
+        assert_render_equal(_host(got), want, f"{len(cams)}-view call")
+
+
+def test_views_aux_and_stats(device, monkeypatch):
+    """rtp_render_views' stats are the totals over all views; the seed and
+    live arrays equal the per-view loop's."""
+    nx, ny, spp, depth = 36, 28, 4, 7
+    cams = _hemi(2, 3, keep=[3, 4, 5])
+    n = len(cams) * nx * ny
+    device.set_cornell_box(0)
+    rgba, st = device.render_views(cams, nx, ny, spp, depth)
+    got = _host(_views_device(device, cams, nx, ny, spp, depth))
+    loop = _host(_views_device(device, cams, nx, ny, spp, depth, env={"RTP_VIEWS_BATCH": "0"}, monkeypatch=monkeypatch))
+    assert rgba.shape == (len(cams), nx * ny, 4)
+    assert st.samples == n * spp
+    assert st.live_bounces == int(got[2].astype(np.uint64).sum())
+    assert same_bits_or_both_nan(rgba.reshape(-1, 4)[:, :3], got[0][:, :3]).all()
+    assert np.array_equal(got[1], loop[1]) and np.array_equal(got[2], loop[2])
+
+
+def test_views_fallbacks(device, monkeypatch):
+    """Scenes with a sphere BVH and RTP_DEBUG_STATS=1 take the per-view loop
+    inside the library: the same outputs as one render_device per view."""
+    nx, ny = 64, 64
+    n = nx * ny
+    cams = _hemi(2, 2, keep=[2, 3])
+    device.set_cornell_box(3)
+    try:
+        got = _host(_views_device(device, cams, nx, ny, 1, 50))
+        loop = _host(_views_device(device, cams, nx, ny, 1, 50, env={"RTP_VIEWS_BATCH": "0"}, monkeypatch=monkeypatch))
+        singles = [_single_device(device, cam, nx, ny, 1, 50) for cam in cams]
+    finally:
+        device.set_cornell_box(0)
+    assert_render_equal(got, loop, "1000 spheres: views vs RTP_VIEWS_BATCH=0")
+    for v, want in enumerate(singles):
+        assert_render_equal(tuple(a[v * n:(v + 1) * n] for a in got), want, f"1000 spheres view {v}")
+    plain = _host(_views_device(device, cams, nx, ny, 3, 6))
+    stats = _host(_views_device(device, cams, nx, ny, 3, 6, env={"RTP_DEBUG_STATS": "1"}, monkeypatch=monkeypatch))
+    assert_render_equal(stats, plain, "RTP_DEBUG_STATS=1")
+
+
+def test_views_errors_launch_nothing(device):
+    """n_views = 0 and n_views * nx * ny > INT32_MAX return
+    RTP_ERR_INVALID_ARGUMENT and leave the output buffer untouched."""
+    import torch
+
+    import raytracingtherestofyourlife_amd as rtp
+    from raytracingtherestofyourlife_amd import _lib
+
+    L = _lib.load()
+    views = (_lib.RtpView * 3)()
+    for v in views:
+        v.camera = rtp.default_camera().to_c()
+    out = torch.full((4096, 4), -5.0, dtype=torch.float32, device="cuda")
+    device.set_cornell_box(0)
+    for n_views, nx, ny in ((0, 32, 32), (3, 32768, 32768)):
+        rc = L.rtp_render_views_device(device.handle, views, n_views, nx, ny, 1, 3, ctypes.c_void_p(out.data_ptr()), None,
+                                       None, None)
+        torch.cuda.synchronize()
+        assert rc == _lib.RTP_ERR_INVALID_ARGUMENT, (n_views, nx, ny, rc)
+        assert L.rtp_last_error()
+        assert bool((out == -5.0).all())
+    assert L.rtp_render_views_device(device.handle, None, 2, 32, 32, 1, 3, ctypes.c_void_p(out.data_ptr()), None, None,
+                                     None) == _lib.RTP_ERR_INVALID_ARGUMENT
+    assert bool((out == -5.0).all())
+
+
+def test_rtp_path_view_batches_write_the_same_files(tmp_path):
+    """rtp_path -hemisphere with the default batch, -viewbatch 0 (the per-view
+    loop) and -viewbatch 4 (which does not divide the 6 views): the same six
+    .pnm and .f32 files, byte for byte."""
+    exe = os.path.join(ROOT, "examples", "rtp_path")
+    base = [exe, "-hemisphere", "-phicount", "2", "-thetacount", "3", "-x", "32", "-y", "32", "-samplecount", "4",
+            "-raydepth", "5", "-raw", "r"]
+    runs = {}
+    for name, extra in (("default", []), ("loop", ["-viewbatch", "0"]), ("four", ["-viewbatch", "4"])):
+        d = tmp_path / name
+        d.mkdir()
+        res = subprocess.run(base + extra, cwd=d, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr
+        runs[name] = {f: (d / f).read_bytes() for f in sorted(os.listdir(d))}
+    names = sorted(runs["loop"])
+    assert len([f for f in names if f.endswith(".pnm")]) == 6 and len([f for f in names if f.endswith(".f32")]) == 6
+    for name in ("default", "four"):
+        assert sorted(runs[name]) == names
+        for f in names:
+            assert runs[name][f] == runs["loop"][f], f"{name}: {f} differs from the per-view loop's"

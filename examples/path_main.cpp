@@ -7,6 +7,7 @@
 //            [-hemisphere [-phicount 15] [-thetacount 15]]
 //            [-o output] [-raw prefix] [-variant 0] [-device 0]
 //            [-rank 0 -world 1] [-dry-run] [-viewbatch N]
+//            [-passes N [-preview]]
 //
 // Writes <o>.pnm like main.cc, or <o>-<phi>-<theta>.pnm per hemisphere view
 // (generate(), "%.4f" formatting).  -raw additionally dumps the normalised
@@ -18,6 +19,13 @@
 // batch one launch (rtp::runPathViews); default: all of the rank's views,
 // capped so that a batch has at most 2^31-1 pixels and under 1 GiB of output;
 // 0: one launch per view (runPath).  The files are the same bytes either way.
+// -passes N: the single view's -samplecount rendered in N resumable passes
+// (rtp::runPathProgressive), the pass sizes as equal as possible with the
+// earlier passes taking the remainder; <o>.pnm and the -raw dump are the same
+// bytes as without -passes.  -preview writes <o>-pass<i>.pnm (i from 1) after
+// each pass: the image of the samples so far.  With -dry-run the pass sizes
+// are printed, one line, and nothing is rendered.  -passes with -hemisphere or
+// -direct, or N < 1, is an error (exit code 2).
 // -direct: the quad mappers' one-bounce AOVs (main.cc:623-651, generate()
 // :399-420): direct.pnm, depth.pnm, normals.pnm, albedo.pnm (or
 // direct-<phi>-<theta>.pnm ... per hemisphere view), all four from one launch.
@@ -74,7 +82,8 @@ uint32_t bits(float f) {
 int main(int argc, char** argv) {
   int x = 128, y = 128, s = 10, depth = 5, variant = 0, device = 0;  // main.cc:56-62 defaults
   int phiCount = 15, thetaCount = 15, rank = 0, world = 1, viewBatch = -1;
-  bool hemi = false, dry = false, direct = false;
+  bool hemi = false, dry = false, direct = false, preview = false, havePasses = false;
+  int passes = 1;
   std::string out = "output", raw;
   for (int i = 1; i < argc; i++) {
     auto next = [&](const char* flag) -> const char* {
@@ -95,6 +104,8 @@ int main(int argc, char** argv) {
     else if ((v = next("-rank"))) rank = std::atoi(v);
     else if ((v = next("-world"))) world = std::atoi(v);
     else if ((v = next("-viewbatch"))) viewBatch = std::atoi(v);
+    else if ((v = next("-passes"))) passes = std::atoi(v), havePasses = true;
+    else if (!std::strcmp(argv[i], "-preview")) preview = true;
     else if (!std::strcmp(argv[i], "-hemisphere")) hemi = true;
     else if (!std::strcmp(argv[i], "-dry-run")) dry = true;
     else if (!std::strcmp(argv[i], "-direct")) direct = true;
@@ -102,6 +113,18 @@ int main(int argc, char** argv) {
   if (world < 1 || rank < 0 || rank >= world || phiCount < 1 || thetaCount < 1) {
     std::cerr << "rtp_path: bad -rank/-world/-phicount/-thetacount" << std::endl;
     return 2;
+  }
+  if (havePasses && (passes < 1 || hemi || direct)) {
+    std::cerr << "rtp_path: -passes needs N >= 1 and renders the single view (no -hemisphere, no -direct)"
+              << std::endl;
+    return 2;
+  }
+  if (havePasses && dry) {
+    if (s < 0) return 2;
+    const std::vector<int> sizes = rtp::SplitPasses(s, passes);
+    for (size_t i = 0; i < sizes.size(); i++) std::printf(i ? " %d" : "%d", sizes[i]);
+    std::printf("\n");
+    return 0;
   }
   std::vector<View> views;
   if (hemi) {
@@ -141,7 +164,13 @@ int main(int argc, char** argv) {
         rtp::SavePNM("albedo" + suffix + ".pnm", b.albedo, x, y);
         return;
       }
-      rtp::runPath(x, y, s, depth, canvas, cam, cb, dev);
+      if (havePasses) {
+        rtp::runPathProgressive(x, y, s, depth, canvas, cam, cb, passes, dev, [&](int i) {
+          if (preview) rtp::SavePNM(out + "-pass" + std::to_string(i + 1) + ".pnm", canvas);
+        });
+      } else {
+        rtp::runPath(x, y, s, depth, canvas, cam, cb, dev);
+      }
       save(suffix);
     };
     auto suffix_of = [](const View& w) {

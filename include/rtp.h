@@ -102,7 +102,9 @@ typedef struct {
   double kernel_ms;      /* device time of the render kernel(s) */
 } rtp_stats;
 
-/* optional per-pixel diagnostics (device or host pointers matching the call) */
+/* optional per-pixel outputs (device or host pointers matching the call):
+ * diagnostics, and with the rgb sums the state a render is continued from
+ * (rtp_render_state below: seed = final_seed) */
 typedef struct {
   uint32_t* final_seed;   /* RNG state after the last sample (nullable) */
   uint32_t* live_bounces; /* live ray-bounces per pixel (nullable) */
@@ -201,6 +203,55 @@ rtp_status rtp_render_views_device(rtp_context* ctx, const rtp_view* views, int3
  * the totals over all views. */
 rtp_status rtp_render_views(rtp_context* ctx, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
                             int32_t spp, int32_t depth, float* rgba_out, rtp_stats* stats);
+
+/* ------------------------------------------------------------------------
+ * Progressive rendering: a render cut along its samples.  A render state over
+ * a pixel set (a contiguous range or a pixel list, as in rtp_render_device)
+ * holds per entry the running un-normalised rgb sums (w is written 0), the
+ * RNG state before the pixel's next sample, optionally the running live-bounce
+ * count and optionally m2, the running second moment of the samples'
+ * luminance: once per finished sample, in sample order, in float without
+ * contraction, with c the sample's radiance (the value added to the sums),
+ *   y = (0.2126f*c.x + 0.7152f*c.y) + 0.0722f*c.z;   m2 = m2 + y*y
+ * (a NaN sample makes m2 NaN; passing m2 changes nothing else).
+ * A fresh state is sums 0, seed = seed_base + pixel (uint32 wrap), live 0,
+ * m2 0; the arrays of an rtp_render_device call with aux (d_rgba_out,
+ * final_seed, live_bounces) are a state too.  A pass renders spp more samples
+ * of every entry and updates the state in place.  For every split
+ * spp = s1 + ... + sn (si >= 0) a fresh state resumed n times equals
+ * rtp_render_device(spp) on the same pixel set bit for bit: rgb sums, final
+ * seeds, live counts.  spp = 0 leaves the state untouched.  Each pass is
+ * limited to 8388607 samples, their total is not. */
+typedef struct {
+  float* rgba;            /* in/out float4[pixel_count]; required */
+  uint32_t* seed;         /* in/out; required */
+  uint32_t* live_bounces; /* in/out, nullable: this pass's count is added */
+  float* m2;              /* in/out, nullable */
+} rtp_render_state;
+
+/* d_state: host struct of device arrays (read before the call returns).
+ * Asynchronous like rtp_render_device: the state is read and written in
+ * stream order, so passes queued back to back on one stream chain without a
+ * host synchronisation, and calls on different states each update their own;
+ * stats != NULL synchronises (samples and kernel_ms).  Every entry is owned by
+ * one pixel slot of the launch, read once and written once: a pixel list with
+ * a repeated id gives each of its entries its own state.  The pool kernel's
+ * resume instances serve scenes without a sphere BVH and the global sphere
+ * walk, each with and without work stealing (RTP_STEAL=0 keeps its meaning);
+ * a scene set with RTP_BVH_LDS=1 renders its passes through the global walk,
+ * with the same results.  RTP_ERR_INVALID_ARGUMENT, nothing launched and the
+ * state untouched: RTP_KERNEL=1 or RTP_DEBUG_STATS=1 in the environment, a
+ * NULL d_state, rgba or seed, a bad camera or size, a range outside the
+ * canvas. */
+rtp_status rtp_render_resume_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
+                                    int32_t depth, int64_t pixel_begin, int64_t pixel_count,
+                                    const int64_t* d_pixel_ids, const rtp_render_state* d_state, void* hip_stream,
+                                    rtp_stats* stats);
+/* Host arrays, synchronous.  pixel_ids NULL: the whole canvas in buffer order
+ * (pixel_count must be nx*ny). */
+rtp_status rtp_render_resume(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
+                             int32_t depth, const int64_t* pixel_ids, int64_t pixel_count,
+                             const rtp_render_state* host_state, rtp_stats* stats);
 
 /* Host-side helpers of the application layer (main.cc). */
 rtp_status rtp_normalize(float* rgba, int64_t n_pixels, int32_t spp);

@@ -174,6 +174,24 @@ class Device {
     return out;
   }
 
+  // rtp_render_resume: spp more samples of every entry of a host-resident
+  // render state (include/rtp.h rtp_render_state), in place.  rgba: the
+  // running sums; seed: the RNG states; live, m2: nullable.  pixel_ids empty:
+  // the whole nx x ny canvas in buffer order.
+  void RenderResume(const rtp_camera& camera, int nx, int ny, int spp, int depthcount, std::vector<Vec4f>& rgba,
+                    std::vector<uint32_t>& seed, std::vector<uint32_t>* live = nullptr,
+                    std::vector<float>* m2 = nullptr, const std::vector<int64_t>& pixel_ids = {},
+                    rtp_stats* stats = nullptr) const {
+    const size_t n = rgba.size();
+    if (seed.size() != n || (live && live->size() != n) || (m2 && m2->size() != n) ||
+        (!pixel_ids.empty() && pixel_ids.size() != n))
+      throw ErrorBadValue("RenderResume: the state arrays and the pixel list must have one entry per pixel");
+    const rtp_render_state st{n ? rgba.data()->data() : nullptr, seed.data(), live ? live->data() : nullptr,
+                              m2 ? m2->data() : nullptr};
+    Check(rtp_render_resume(get(), &camera, nx, ny, spp, depthcount, pixel_ids.empty() ? nullptr : pixel_ids.data(),
+                            (int64_t)n, &st, stats));
+  }
+
  private:
   std::shared_ptr<rtp_context> ctx_;
 };
@@ -450,6 +468,14 @@ class MapperPathTracer {
     std::vector<Vec4f> out = internals_->device->RenderViews(cams, nx, ny, samplecount, depthcount, {}, &st);
     last_stats = st;
     return out;
+  }
+
+  // The scene of RenderCells uploaded without a render (ProgressiveRender
+  // renders it in passes); returns the mapper's device.
+  std::shared_ptr<Device> UploadScene(const CellSet& cellset, const CoordinateSystem& coords) {
+    SetScene(cellset, coords);
+    device();
+    return internals_->device;
   }
 
   const int samplecount, depthcount;  // as in the reference: (sc, dc)
@@ -748,6 +774,90 @@ inline std::vector<Vec4f> runPathViews(int nx, int ny, int samplecount, int dept
   std::vector<Vec4f> out = mapper.RenderCellsViews(cb.ds.GetCellSet(), cb.coord, cams, nx, ny);
   Normalize(out, samplecount);
   return out;
+}
+
+// samplecount cut into `passes` pass sizes as equal as possible, the earlier
+// passes taking the remainder (10 in 3: 4, 3, 3).
+inline std::vector<int> SplitPasses(int samplecount, int passes) {
+  if (passes < 1) throw ErrorBadValue("SplitPasses: passes must be >= 1");
+  if (samplecount < 0) throw ErrorBadValue("SplitPasses: samplecount must be >= 0");
+  std::vector<int> sizes((size_t)passes, samplecount / passes);
+  for (int i = 0; i < samplecount % passes; i++) sizes[(size_t)i]++;
+  return sizes;
+}
+
+// A canvas rendered in passes (rtp_render_resume): the render state of every
+// pixel of the device's current scene -- running rgb sums, RNG states, live
+// counts and the second moment of the samples' luminance.  After any passes
+// the state equals one rtp_render of Samples() samples bit for bit.  This
+// header is host C++ over the C ABI alone, so the state lives in host memory
+// and each Step uploads and reads it back; rtp_render_resume_device (and the
+// Python ProgressiveRender) keep it on the device.
+class ProgressiveRender {
+ public:
+  ProgressiveRender(std::shared_ptr<Device> device, const rendering::Camera& camera, int nx, int ny, int depthcount,
+                    uint32_t seed_base = 0)
+      : device_(std::move(device)), cam_(camera.ToC()), nx_(nx), ny_(ny), depth_(depthcount) {
+    if (!device_) throw ErrorBadValue("ProgressiveRender: no device");
+    if (nx <= 0 || ny <= 0) throw ErrorBadValue("Camera width/height must be greater than zero.");
+    const size_t n = (size_t)nx * (size_t)ny;
+    sums_.assign(n, Vec4f{});
+    seed_.resize(n);
+    for (size_t i = 0; i < n; i++) seed_[i] = seed_base + (uint32_t)i;  // seeds[i] = i (uint32 wrap)
+    live_.assign(n, 0u);
+    m2_.assign(n, 0.f);
+  }
+  // spp more samples of every pixel
+  void Step(int spp, rtp_stats* stats = nullptr) {
+    device_->RenderResume(cam_, nx_, ny_, spp, depth_, sums_, seed_, &live_, &m2_, {}, stats);
+    samples_ += spp;
+  }
+  int64_t Samples() const { return samples_; }
+  // the normalised colours of the samples so far (rtp_normalize) into a canvas of the same size
+  void Canvas(rendering::CanvasRayTracer& canvas) const {
+    if (canvas.GetWidth() != nx_ || canvas.GetHeight() != ny_)
+      throw ErrorBadValue("ProgressiveRender::Canvas: the canvas must be nx x ny");
+    if (samples_ > INT32_MAX) throw ErrorBadValue("ProgressiveRender::Canvas: more than 2^31-1 samples");
+    canvas.GetColorBuffer().assign(sums_.begin(), sums_.end());
+    Normalize(canvas.GetColorBuffer(), (int)samples_);
+  }
+  const std::vector<Vec4f>& Sums() const { return sums_; }
+  const std::vector<uint32_t>& Seeds() const { return seed_; }
+  const std::vector<uint32_t>& LiveBounces() const { return live_; }
+  const std::vector<float>& M2() const { return m2_; }
+
+ private:
+  std::shared_ptr<Device> device_;
+  rtp_camera cam_;
+  int nx_, ny_, depth_;
+  int64_t samples_ = 0;
+  std::vector<Vec4f> sums_;
+  std::vector<uint32_t> seed_, live_;
+  std::vector<float> m2_;
+};
+
+// runPath rendered in `passes` passes (SplitPasses): the canvas ends with
+// runPath's colours, bit for bit.  on_pass(i), when given, is called after
+// pass i with the canvas holding the normalised image so far (a preview).
+template <class OnPass>
+inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, rendering::CanvasRayTracer& canvas,
+                               rendering::Camera& cam, CornellBox& cb, int passes, std::shared_ptr<Device> device,
+                               OnPass on_pass) {
+  const std::vector<int> sizes = SplitPasses(samplecount, passes);
+  rendering::MapperPathTracer mapper(samplecount, depthcount, cb.matIdx, cb.texIdx, cb.matType, cb.texType, cb.tex,
+                                     std::move(device));
+  mapper.SetLights(cb.lightQuad, cb.lightSphere, cb.ior);
+  ProgressiveRender render(mapper.UploadScene(cb.ds.GetCellSet(), cb.coord), cam, nx, ny, depthcount);
+  for (size_t i = 0; i < sizes.size(); i++) {
+    render.Step(sizes[i]);
+    render.Canvas(canvas);
+    on_pass((int)i);
+  }
+}
+inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, rendering::CanvasRayTracer& canvas,
+                               rendering::Camera& cam, CornellBox& cb, int passes,
+                               std::shared_ptr<Device> device = nullptr) {
+  runPathProgressive(nx, ny, samplecount, depthcount, canvas, cam, cb, passes, std::move(device), [](int) {});
 }
 
 }  // namespace rtp

@@ -4,8 +4,9 @@ kernels for gfx950 behind a C ABI (include/rtp.h, librtp.so)."""
 from ._lib import LIB_PATH, RtpError, load  # noqa: F401
 from .mapper import (  # noqa: F401
     Camera, CanvasRayTracer, CellSet, CornellBox, DataSet, Device, ErrorBadValue, MapperPathTracer,
-    Field, default_camera, hemisphere_cameras, normalize, runPath, runPathViews, save_pnm,
+    Field, default_camera, hemisphere_cameras, normalize, runPath, runPathProgressive, runPathViews, save_pnm,
 )
+from .progressive import ProgressiveRender, noise_from_state, select_active, split_passes  # noqa: F401
 from .direct import (  # noqa: F401
     Actor, Color, ColorTable, MapperQuad, MapperQuadAlbedo, MapperQuadNormals, Scene, View3D, runAlbedo,
     runDirect, runNorms, runRay, save_depth_pnm,
@@ -16,4 +17,5 @@ __all__ = [
     "MapperPathTracer", "RtpError", "default_camera", "load", "normalize", "runPath", "save_pnm", "LIB_PATH",
     "Field", "Actor", "Color", "ColorTable", "MapperQuad", "MapperQuadAlbedo", "MapperQuadNormals", "Scene",
     "View3D", "runAlbedo", "runDirect", "runNorms", "runRay", "save_depth_pnm", "hemisphere_cameras", "runPathViews",
+    "runPathProgressive", "ProgressiveRender", "noise_from_state", "select_active", "split_passes",
 ]

@@ -55,6 +55,12 @@ class RtpPixelAux(ctypes.Structure):
     _fields_ = [("final_seed", u32p), ("live_bounces", u32p)]
 
 
+class RtpRenderState(ctypes.Structure):
+    """rtp_render_state: the arrays a render is continued from (device or host
+    pointers matching the call)."""
+    _fields_ = [("rgba", f32p), ("seed", u32p), ("live_bounces", u32p), ("m2", f32p)]
+
+
 class RtpDirectDesc(ctypes.Structure):
     _fields_ = [("clip_near", ctypes.c_float), ("clip_far", ctypes.c_float), ("background", ctypes.c_float * 4),
                 ("composite_background", ctypes.c_int32), ("quad_scalar", f32p), ("color_map", f32p),
@@ -79,7 +85,7 @@ EXPORTED_SYMBOLS = [
     "rtp_render_direct", "rtp_render_direct_device", "rtp_sample_color_table", "rtp_quad_scalars",
     "rtp_cornell_point_field", "rtp_write_pnm_depth", "rtp_eval_powf", "rtp_set_ff_tables", "rtp_get_ff_tables",
     "rtp_render_planned_device", "rtp_sphere_walk", "rtp_sphere_walk_oct_mask",
-    "rtp_render_views_device", "rtp_render_views",
+    "rtp_render_views_device", "rtp_render_views", "rtp_render_resume_device", "rtp_render_resume",
 ]
 
 
@@ -160,6 +166,17 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     # them raises AttributeError.  The in-tree library must export them.
     older = bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_render_views_device")
     skip = ("rtp_render_views_device", "rtp_render_views") if older else ()
+    # (likewise a revision before the resumable render: tools/progressive_bench.py's baseline)
+    no_resume = bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_render_resume_device")
+    if no_resume:
+        skip += ("rtp_render_resume_device", "rtp_render_resume")
+    else:
+        L.rtp_render_resume_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
+                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp,
+                                               ctypes.POINTER(RtpRenderState), vp, ctypes.POINTER(RtpStats)]
+        L.rtp_render_resume.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_int32, ctypes.c_int32, i64p, ctypes.c_int64,
+                                        ctypes.POINTER(RtpRenderState), ctypes.POINTER(RtpStats)]
     if not older:
         L.rtp_render_views_device.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32,
                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp,

@@ -1047,7 +1047,7 @@ rtp_status launch(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny,
                   uint32_t seed_base, int64_t pixel_begin, int64_t npix, const int64_t* d_ids, float* d_out,
                   uint32_t* d_seed, uint32_t* d_live, hipStream_t stream, double* kernel_ms,
                   const int32_t* tile = nullptr, const int32_t* d_wave_begin = nullptr, int plan_waves = 0,
-                  const rtp::DevView* d_views = nullptr) {
+                  const rtp::DevView* d_views = nullptr, bool resume = false, float* d_m2 = nullptr) {
   // the kernels index a launch's entries with 32-bit integers
   if (npix > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render: more than 2^31-1 pixels in one launch");
   HIP_TRY(hipSetDevice(c->device));
@@ -1064,12 +1064,15 @@ rtp_status launch(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny,
   p.out = d_out;
   p.seed_out = d_seed;
   p.live_out = d_live;
+  p.resume = resume ? 1 : 0;  // a pass over a render state: d_out, d_seed, d_live, d_m2 are read and updated
+  p.m2 = d_m2;
   int variant = 2, waves = 0;
   // the sphere BVH's walk: 2 out of LDS when the tree fits (rtp_render_pool_lds),
   // 1 the global threaded walk (also for the diagnostics build and wave plans)
   const char* stats_env = getenv("RTP_DEBUG_STATS");
   const bool stats_on = stats_env && stats_env[0] == '1';
-  const int bvh = !c->use_bvh ? 0 : (c->lw_bytes > 0 && !stats_on && !d_wave_begin) ? 2 : 1;
+  // (a resume pass has no LDS-walk instance: the global walk, same results)
+  const int bvh = !c->use_bvh ? 0 : (c->lw_bytes > 0 && !stats_on && !d_wave_begin && !resume) ? 2 : 1;
   int64_t lanes = rtp_plan_history_lanes(npix, spp, bvh, &variant, &waves);
   if (d_wave_begin) {  // a planned launch: the caller's waves
     if (variant != 2 || c->use_bvh || tile)
@@ -1182,6 +1185,23 @@ rtp_status render_host(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_
     stats->nan_pixels = nan;
     stats->kernel_ms = ms;
   }
+  return RTP_OK;
+}
+
+// the checks of rtp_render_resume* before their pixel sets
+rtp_status check_resume_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
+                             int32_t depth, const rtp_render_state* st, const char* who) {
+  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
+  if (rs != RTP_OK) return rs;
+  if (!st || !st->rgba || !st->seed)
+    return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": state, state->rgba and state->seed are required");
+  auto is1 = [](const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '1';
+  };
+  if (is1("RTP_KERNEL")) return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with RTP_KERNEL=1");
+  if (is1("RTP_DEBUG_STATS"))
+    return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with RTP_DEBUG_STATS=1");
   return RTP_OK;
 }
 
@@ -1299,6 +1319,88 @@ rtp_status rtp_render_tiles_device(rtp_context* c, const rtp_camera* cam, int32_
     stats->samples = (uint64_t)mine * 256 * (uint64_t)spp;
     stats->live_bounces = 0;
     stats->nan_pixels = 0;
+    stats->kernel_ms = ms;
+  }
+  return rs;
+}
+
+// One more pass of spp samples over a render state (include/rtp.h): the pool
+// kernel's kResume instances gather each entry's state and write it back.
+rtp_status rtp_render_resume_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
+                                    int32_t depth, int64_t pixel_begin, int64_t pixel_count,
+                                    const int64_t* d_pixel_ids, const rtp_render_state* d_state, void* hip_stream,
+                                    rtp_stats* stats) {
+  rtp_status rs = check_resume_args(c, cam, nx, ny, spp, depth, d_state, "rtp_render_resume_device");
+  if (rs != RTP_OK) return rs;
+  if (pixel_count < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume_device: pixel_count < 0");
+  if (!d_pixel_ids && (pixel_begin < 0 || pixel_begin + pixel_count > (int64_t)nx * ny))
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume_device: pixel range outside the canvas");
+  if (stats) *stats = rtp_stats{};
+  if (pixel_count == 0 || spp == 0) return RTP_OK;  // (no samples: the state stays as it is)
+  double ms = 0;
+  rs = launch(c, cam, nx, ny, spp, depth, 0u, pixel_begin, pixel_count, d_pixel_ids, d_state->rgba, d_state->seed,
+              d_state->live_bounces, (hipStream_t)hip_stream, stats ? &ms : nullptr, nullptr, nullptr, 0, nullptr, true,
+              d_state->m2);
+  if (rs == RTP_OK && stats) {
+    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
+    stats->kernel_ms = ms;
+  }
+  return rs;
+}
+
+// Host arrays, synchronous: the state is uploaded, resumed and copied back.
+rtp_status rtp_render_resume(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
+                             int32_t depth, const int64_t* pixel_ids, int64_t pixel_count,
+                             const rtp_render_state* host_state, rtp_stats* stats) {
+  rtp_status rs = check_resume_args(c, cam, nx, ny, spp, depth, host_state, "rtp_render_resume");
+  if (rs != RTP_OK) return rs;
+  const int64_t npx = (int64_t)nx * ny;
+  if (pixel_count < 0 || (!pixel_ids && pixel_count != npx))
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume: without a pixel list pixel_count must be nx * ny");
+  for (int64_t i = 0; pixel_ids && i < pixel_count; i++)
+    if (pixel_ids[i] < 0 || pixel_ids[i] >= npx)
+      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume: pixel id out of range");
+  if (stats) *stats = rtp_stats{};
+  if (pixel_count == 0 || spp == 0) return RTP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)pixel_count;
+  int64_t* d_ids = nullptr;
+  rtp_render_state d{};
+  auto cleanup = [&]() {
+    if (d_ids) (void)hipFree(d_ids);
+    if (d.rgba) (void)hipFree(d.rgba);
+    if (d.seed) (void)hipFree(d.seed);
+    if (d.live_bounces) (void)hipFree(d.live_bounces);
+    if (d.m2) (void)hipFree(d.m2);
+  };
+  auto up = [&](auto** dst, const auto* src, size_t bytes) {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), bytes);
+    if (e == hipSuccess) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+    return e;
+  };
+  hipError_t e = up(&d.rgba, host_state->rgba, n * 16);
+  if (e == hipSuccess) e = up(&d.seed, host_state->seed, n * 4);
+  if (e == hipSuccess && host_state->live_bounces) e = up(&d.live_bounces, host_state->live_bounces, n * 4);
+  if (e == hipSuccess && host_state->m2) e = up(&d.m2, host_state->m2, n * 4);
+  if (e == hipSuccess && pixel_ids) e = up(&d_ids, pixel_ids, n * 8);
+  if (e != hipSuccess) {
+    cleanup();
+    return hip_fail(e, "render_resume: device buffers");
+  }
+  double ms = 0;
+  rs = launch(c, cam, nx, ny, spp, depth, 0u, 0, pixel_count, d_ids, d.rgba, d.seed, d.live_bounces, nullptr, &ms,
+              nullptr, nullptr, 0, nullptr, true, d.m2);
+  if (rs == RTP_OK) {
+    e = hipMemcpy(host_state->rgba, d.rgba, n * 16, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(host_state->seed, d.seed, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && d.live_bounces)
+      e = hipMemcpy(host_state->live_bounces, d.live_bounces, n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && d.m2) e = hipMemcpy(host_state->m2, d.m2, n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rs = hip_fail(e, "render_resume: copy back");
+  }
+  cleanup();
+  if (rs == RTP_OK && stats) {
+    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
     stats->kernel_ms = ms;
   }
   return rs;

@@ -1007,11 +1007,19 @@ typedef const __attribute__((address_space(1))) uint32_t GU32;
 // deal and under stealing, so the camera is per lane -- each refill gathers
 // its view's DevCamera from the global table (three 16-byte loads; the table
 // of a hemisphere sweep is ~14 KB and stays in the vector L1 / L2).
+// kResume: one more pass over a render state (rtp_render_resume_device).  An
+// entry's seed, sums, live count and second moment are gathered from the
+// state arrays (KParams::out, seed_out, live_out, m2) where the other
+// instances compute or zero them, and written back by the unchanged write-out:
+// each entry is owned by one slot, read once before its first sample of the
+// pass and written once after its last.  s_samples counts the pass's samples.
+// The second moment of the samples' luminance runs in a fifth float per slot
+// (s_m2_all), added where the sample is added to the sums.
 template <bool kStats, bool kBvh, bool kTiles, bool kPlan, int kWPB, bool kLdsBvh, bool kSteal = false,
-          bool kViews = false>
+          bool kViews = false, bool kResume = false>
 __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const KParams& p, int n_waves,
                                           unsigned char* smem, float* s_qshade, uint32_t* s_bvh,
-                                          uint32_t* s_entry_all = nullptr) {
+                                          uint32_t* s_entry_all = nullptr, float* s_m2_all = nullptr) {
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
   const int w = blockIdx.x * kWPB + wib;  // global wave id
@@ -1038,6 +1046,7 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
   uint16_t* q_ready = s_rem + kPool;
   uint16_t* q_ff = q_ready + kPool;
   uint32_t* s_entry = kSteal ? s_entry_all + wib * kPool : nullptr;  // kSteal: the slot's entry
+  float* s_m2 = kResume ? s_m2_all + wib * kPool : nullptr;          // kResume: the slot's second moment
 
   const uint32_t t1 = sc->which_t1, t2 = sc->which_t2;
   const int D = p.depth, S = p.spp;
@@ -1054,13 +1063,24 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
   for (int j = lane; j < n_slots; j += 64) {
     const int64_t k = kPlan ? (int64_t)(wbase + j) : (int64_t)j * n_waves + w;
     if constexpr (kSteal) s_entry[j] = (uint32_t)k;
-    if constexpr (kViews) s_seed[j] = view_seed(p, (int)k);
-    else s_seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
-    s_r[j] = 0.f;
-    s_g[j] = 0.f;
-    s_b[j] = 0.f;
-    s_samples[j] = 0u;
-    s_live[j] = 0u;
+    if constexpr (kResume) {  // the entry's state so far
+      const float4 v = reinterpret_cast<const float4*>(p.out)[k];
+      s_seed[j] = p.seed_out[k];
+      s_r[j] = v.x;
+      s_g[j] = v.y;
+      s_b[j] = v.z;
+      s_samples[j] = 0u;
+      s_live[j] = p.live_out ? p.live_out[k] : 0u;
+      s_m2[j] = p.m2 ? p.m2[k] : 0.f;
+    } else {
+      if constexpr (kViews) s_seed[j] = view_seed(p, (int)k);
+      else s_seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
+      s_r[j] = 0.f;
+      s_g[j] = 0.f;
+      s_b[j] = 0.f;
+      s_samples[j] = 0u;
+      s_live[j] = 0u;
+    }
     s_rem[j] = 0;
     q_ready[j] = (uint16_t)j;
   }
@@ -1214,6 +1234,10 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
         s_r[fslot] = s_r[fslot] + c.x;  // cols += sumtotl (MapperPathTracer.cxx:350), in sample order
         s_g[fslot] = s_g[fslot] + c.y;
         s_b[fslot] = s_b[fslot] + c.z;
+        if constexpr (kResume) {  // m2 += y * y, y the sample's luminance (include/rtp.h rtp_render_state)
+          const float y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+          s_m2[fslot] = s_m2[fslot] + y * y;
+        }
       }
       // jump over 32 / 16 / 8 / 4 dead depths with one table read each
       // (HBM-resident tables of the dead-step map, built once per device),
@@ -1264,16 +1288,29 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
             reinterpret_cast<float4*>(p.out)[k] = make_float4(s_r[fslot], s_g[fslot], s_b[fslot], 0.f);
             if (p.seed_out) p.seed_out[k] = s_seed[fslot];
             if (p.live_out) p.live_out[k] = s_live[fslot];
+            if constexpr (kResume)
+              if (p.m2) p.m2[k] = s_m2[fslot];
             const unsigned long long kn = base + lane_rank(done);
             if (kn < (unsigned long long)p.npix) {  // a fresh pixel in this slot, at the front of READY below
               s_entry[fslot] = (uint32_t)kn;
-              if constexpr (kViews) s_seed[fslot] = view_seed(p, (int)kn);
-              else s_seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
-              s_r[fslot] = 0.f;
-              s_g[fslot] = 0.f;
-              s_b[fslot] = 0.f;
-              s_samples[fslot] = 0u;
-              s_live[fslot] = 0u;
+              if constexpr (kResume) {  // the claimed entry's state so far
+                const float4 v = reinterpret_cast<const float4*>(p.out)[kn];
+                s_seed[fslot] = p.seed_out[kn];
+                s_r[fslot] = v.x;
+                s_g[fslot] = v.y;
+                s_b[fslot] = v.z;
+                s_samples[fslot] = 0u;
+                s_live[fslot] = p.live_out ? p.live_out[kn] : 0u;
+                s_m2[fslot] = p.m2 ? p.m2[kn] : 0.f;
+              } else {
+                if constexpr (kViews) s_seed[fslot] = view_seed(p, (int)kn);
+                else s_seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
+                s_r[fslot] = 0.f;
+                s_g[fslot] = 0.f;
+                s_b[fslot] = 0.f;
+                s_samples[fslot] = 0u;
+                s_live[fslot] = 0u;
+              }
               s_rem[fslot] = 0;
               again = true;
             }
@@ -1489,6 +1526,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     reinterpret_cast<float4*>(p.out)[k] = make_float4(s_r[j], s_g[j], s_b[j], 0.f);
     if (p.seed_out) p.seed_out[k] = s_seed[j];
     if (p.live_out) p.live_out[k] = s_live[j];
+    if constexpr (kResume)
+      if (p.m2) p.m2[k] = s_m2[j];
   }
 }
 
@@ -1497,13 +1536,26 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
 #else
 #define RTP_POOL_VGPR_ATTR
 #endif
-template <bool kStats, bool kBvh, bool kTiles = false, bool kPlan = false, bool kSteal = false, bool kViews = false>
+template <bool kStats, bool kBvh, bool kTiles = false, bool kPlan = false, bool kSteal = false, bool kViews = false,
+          bool kResume = false>
 __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_ATTR
     rtp_render_pool(const DevScene* __restrict__ sc, KParams p, int n_waves) {
   static_assert(!kViews || (!kStats && !kBvh && !kTiles && !kPlan), "batched views: the plain and stealing instances");
+  static_assert(!kResume || (!kStats && !kTiles && !kPlan && !kViews),
+                "resume: {no BVH, global sphere walk} x {plain, stealing}; no stats, wave plan, tile deal or views");
   __shared__ __align__(16) unsigned char smem[kPoolLdsBytes];
   __shared__ __align__(16) float s_qshade[kQTableFloats];
-  if constexpr (kSteal) {
+  if constexpr (kResume) {  // (+2 KiB a block: 5 blocks per CU still fit)
+    __shared__ float s_m2[kWavesPerBlock * kPool];
+    if constexpr (kSteal) {
+      __shared__ uint32_t s_entry[kWavesPerBlock * kPool];
+      pool_body<false, kBvh, false, false, kWavesPerBlock, false, true, false, true>(sc, p, n_waves, smem, s_qshade,
+                                                                                     nullptr, s_entry, s_m2);
+    } else {
+      pool_body<false, kBvh, false, false, kWavesPerBlock, false, false, false, true>(sc, p, n_waves, smem, s_qshade,
+                                                                                      nullptr, nullptr, s_m2);
+    }
+  } else if constexpr (kSteal) {
     __shared__ uint32_t s_entry[kWavesPerBlock * kPool];
     pool_body<kStats, kBvh, kTiles, kPlan, kWavesPerBlock, false, true, kViews>(sc, p, n_waves, smem, s_qshade,
                                                                                 nullptr, s_entry);
@@ -1816,7 +1868,7 @@ extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const 
 extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves,
                                         int bvh, hipStream_t stream, int lds_bytes) {
   if (p->npix <= 0) return hipSuccess;
-  if (variant == 1 && (p->tile_world > 0 || p->views)) return hipErrorNotSupported;  // (v1 takes pixel lists or ranges)
+  if (variant == 1 && (p->tile_world > 0 || p->views || p->resume)) return hipErrorNotSupported;  // (v1 takes pixel lists or ranges)
   if (variant == 1) {
     const int64_t grid = (p->npix + 255) / 256;
     if (bvh)
@@ -1824,7 +1876,7 @@ extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::K
     else
       hipLaunchKernelGGL(rtp::rtp_render_lockstep<false>, dim3((unsigned)grid), dim3(256), 0, stream, scene, *p);
   } else if (bvh == 2) {  // the sphere BVH walked out of LDS
-    if (p->wave_begin || p->views || lds_bytes <= 0 || lds_bytes > rtp::kLdsWalkDynBytes) return hipErrorNotSupported;
+    if (p->wave_begin || p->views || p->resume || lds_bytes <= 0 || lds_bytes > rtp::kLdsWalkDynBytes) return hipErrorNotSupported;
     (void)lds_bvh_resident_blocks_per_cu();  // (sets the kernels' dynamic-LDS limit once)
     const int blocks = (waves + rtp::kLdsBvhWavesPerBlock - 1) / rtp::kLdsBvhWavesPerBlock;
     const dim3 g((unsigned)blocks), b(64 * rtp::kLdsBvhWavesPerBlock);
@@ -1839,7 +1891,14 @@ extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::K
     const char* st = getenv("RTP_DEBUG_STATS");
     const bool stats = p->dbg && st && st[0] == '1';
     const dim3 g((unsigned)blocks), b(256);
-    if (p->views) {  // batched views: their own instances (no sphere BVH, stats, plan or tile deal)
+    if (p->resume) {  // a pass over a render state: its own instances (no stats, plan, tile deal or views)
+      if (stats || p->wave_begin || p->tile_world > 0 || p->views || !p->seed_out) return hipErrorNotSupported;
+      const bool steal = (int64_t)waves * rtp::kPool < p->npix;  // rtp_plan_steal
+      if (steal && bvh) hipLaunchKernelGGL((rtp::rtp_render_pool<false, true, false, false, true, false, true>), g, b, 0, stream, scene, *p, waves);
+      else if (steal) hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, false, true, false, true>), g, b, 0, stream, scene, *p, waves);
+      else if (bvh) hipLaunchKernelGGL((rtp::rtp_render_pool<false, true, false, false, false, false, true>), g, b, 0, stream, scene, *p, waves);
+      else hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, false, false, false, true>), g, b, 0, stream, scene, *p, waves);
+    } else if (p->views) {  // batched views: their own instances (no sphere BVH, stats, plan or tile deal)
       if (bvh || stats || p->wave_begin || p->tile_world > 0 || p->pixel_ids) return hipErrorNotSupported;
       if ((int64_t)waves * rtp::kPool < p->npix)  // work stealing (rtp_plan_steal)
         hipLaunchKernelGGL((rtp::rtp_render_pool<false, false, false, false, true, true>), g, b, 0, stream, scene, *p, waves);

@@ -288,6 +288,12 @@ struct KParams {
   // of view k / (nx*ny), view-major; npix = n_views * nx * ny; cam, seed_base,
   // pixel_begin, pixel_ids and the tile deal are unused
   const DevView* views;
+  // a pass over a render state (resume != 0; pool kernel kResume): out,
+  // seed_out (required) and live_out hold each entry's state so far and are
+  // updated in place; m2 (nullable): the running second moment of the samples'
+  // luminance, float[npix]; seed_base is unused
+  float* m2;
+  int32_t resume, resume_pad;
 };
 
 // -direct mode (main.cc:120-251): one launch renders the requested AOVs of

@@ -24,7 +24,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import RtpCamera, RtpFfInfo, RtpPixelAux, RtpSceneDesc, RtpStats, RtpView, check
+from ._lib import RtpCamera, RtpFfInfo, RtpPixelAux, RtpRenderState, RtpSceneDesc, RtpStats, RtpView, check
 
 
 class ErrorBadValue(ValueError):
@@ -382,6 +382,52 @@ class Device:
                                               ctypes.c_void_p(stream or None), ctypes.byref(st) if timed else None))
         return st
 
+    def render_resume_device(self, camera: Camera, nx: int, ny: int, spp: int, depth: int, rgba_ptr: int,
+                             seed_ptr: int, live_ptr: int = 0, m2_ptr: int = 0, pixel_begin: int = 0,
+                             pixel_count: int | None = None, pixel_ids_ptr: int = 0, stream: int = 0,
+                             timed: bool = False):
+        """rtp_render_resume_device: spp more samples of every entry of a
+        device-resident render state (rgba_ptr: float4[pixel_count] running
+        sums, seed_ptr: u32 RNG states; live_ptr, m2_ptr optional), updated in
+        place.  Asynchronous unless timed."""
+        if pixel_count is None:
+            pixel_count = nx * ny - pixel_begin
+        state = RtpRenderState(ctypes.cast(rgba_ptr, _lib.f32p) if rgba_ptr else None,
+                               ctypes.cast(seed_ptr, _lib.u32p) if seed_ptr else None,
+                               ctypes.cast(live_ptr, _lib.u32p) if live_ptr else None,
+                               ctypes.cast(m2_ptr, _lib.f32p) if m2_ptr else None)
+        st = RtpStats()
+        cam = camera.to_c()
+        check(self._L.rtp_render_resume_device(self.handle, ctypes.byref(cam), nx, ny, spp, depth, pixel_begin,
+                                               pixel_count, ctypes.c_void_p(pixel_ids_ptr or None),
+                                               ctypes.byref(state), ctypes.c_void_p(stream or None),
+                                               ctypes.byref(st) if timed else None))
+        return st
+
+    def render_resume(self, camera: Camera, nx: int, ny: int, spp: int, depth: int, rgba: np.ndarray,
+                      seed: np.ndarray, live: np.ndarray | None = None, m2: np.ndarray | None = None, pixels=None):
+        """rtp_render_resume on host arrays, in place: rgba float32 [n, 4],
+        seed uint32 [n], live uint32 [n] and m2 float32 [n] (optional), over
+        the pixel list ``pixels`` (None: the whole canvas).  Returns stats."""
+        n = rgba.shape[0]
+        want = [(rgba, np.float32, (n, 4)), (seed, np.uint32, (n,))]
+        want += [(a, dt, (n,)) for a, dt in ((live, np.uint32), (m2, np.float32)) if a is not None]
+        for a, dt, shape in want:
+            if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == dt and a.shape == shape):
+                raise ErrorBadValue(f"render_resume: expects C-contiguous {np.dtype(dt).name} arrays of shape {shape}")
+        ids = None if pixels is None else np.ascontiguousarray(pixels, dtype=np.int64)
+        if ids is not None and ids.size != n:
+            raise ErrorBadValue(f"render_resume: {ids.size} pixels for a state of {n} entries")
+        state = RtpRenderState(rgba.ctypes.data_as(_lib.f32p), seed.ctypes.data_as(_lib.u32p),
+                               live.ctypes.data_as(_lib.u32p) if live is not None else None,
+                               m2.ctypes.data_as(_lib.f32p) if m2 is not None else None)
+        st = RtpStats()
+        cam = camera.to_c()
+        check(self._L.rtp_render_resume(self.handle, ctypes.byref(cam), nx, ny, spp, depth,
+                                        ids.ctypes.data_as(_lib.i64p) if ids is not None else None, n,
+                                        ctypes.byref(state), ctypes.byref(st)))
+        return st
+
     FF_POLICIES = {"auto": _lib.RTP_FF_TABLES_AUTO, "off": _lib.RTP_FF_TABLES_OFF, "on": _lib.RTP_FF_TABLES_ON}
 
     def sphere_walk(self) -> str:
@@ -567,6 +613,30 @@ def runPathViews(nx: int, ny: int, samplecount: int, depthcount: int, cameras, c
     out, _ = dev.render_views(cameras, nx, ny, samplecount, depthcount)
     normalize(out.reshape(-1, 4), samplecount)
     return out
+
+
+def runPathProgressive(nx: int, ny: int, samplecount: int, depthcount: int, canvas: CanvasRayTracer, cam: Camera,
+                       cb: CornellBox, passes: int, device: int | Device = 0, on_pass=None):
+    """runPath rendered in ``passes`` resumable passes (progressive.split_passes):
+    the canvas receives the same normalised colours as runPath's.  on_pass(i,
+    render), when given, is called after each pass (a preview hook).  Returns
+    the ProgressiveRender."""
+    from .progressive import ProgressiveRender, split_passes
+
+    sizes = split_passes(samplecount, passes)
+    dev = device if isinstance(device, Device) else Device(device)
+    cellset = cb.ds.GetCellSet()
+    dev.set_scene(cb.coord, cellset.quad_points, cb.matIdx[0], cb.texIdx[0], cellset.sphere_points, cb.SphereRadii,
+                  cb.matIdx[1], cb.texIdx[1], cb.matType, cb.texType, cb.tex, cb.light_quad_points,
+                  cb.light_sphere_point, cb.ior)
+    render = ProgressiveRender(dev, cam, nx, ny, depthcount)
+    for i, spp in enumerate(sizes):
+        render.step(spp)
+        if on_pass is not None:
+            on_pass(i, render)
+    canvas.color[...] = render.sums.cpu().numpy()
+    normalize(canvas.GetColorBuffer(), samplecount)
+    return render
 
 
 def hemisphere_cameras(phi_count: int = 15, theta_count: int = 15) -> list:

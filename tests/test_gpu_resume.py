@@ -1,0 +1,418 @@
+"""A render cut along its samples (rtp_render_resume_device; rtp_kernels.hip
+pool_body kResume): a state of running sums, RNG states, live counts and the
+second moment m2 is resumed in passes.  However the samples are split, the
+state must equal rtp_render_device of the total -- rgb sums, final RNG states,
+live-bounce counts, bit for bit -- and the oracle's render; m2 must equal the
+sequential float32 sum of the squared luminances of the oracle's samples."""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from _util import assert_render_equal, same_bits_or_both_nan
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _plan_steal(npix: int, bvh: int = 0) -> int:
+    from raytracingtherestofyourlife_amd import _lib
+
+    L = _lib.load()
+    L.rtp_plan_steal.restype = ctypes.c_int
+    L.rtp_plan_steal.argtypes = [ctypes.c_int64, ctypes.c_int]
+    return L.rtp_plan_steal(npix, bvh)
+
+
+def _cam():
+    import raytracingtherestofyourlife_amd as rtp
+
+    return rtp.default_camera()
+
+
+def _other_cam():
+    import raytracingtherestofyourlife_amd as rtp
+
+    cam = rtp.Camera()
+    cam.SetPosition([0.9, 0.7, -1.1])
+    cam.SetLookAt([0.4, 0.45, 0.55])
+    cam.SetViewUp([0.1, 1.0, 0.05])
+    cam.SetFieldOfView(52.0)
+    return cam
+
+
+def _oracle_cam(oracle, nx, ny, cam):
+    return oracle.camera_setup(nx, ny, position=cam.position, look_at=cam.look_at, view_up=cam.view_up,
+                               fov_y=float(cam.fov))
+
+
+class State:
+    """A fresh device-resident render state over ``pixels`` (ids of the canvas)."""
+
+    def __init__(self, pixels, seed_base=0, m2=True):
+        import torch
+
+        pix = np.ascontiguousarray(pixels, dtype=np.int64)
+        n = pix.size
+        seeds = ((pix.astype(np.uint64) + np.uint64(seed_base)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        self.n = n
+        self.sums = torch.zeros((n, 4), dtype=torch.float32, device="cuda")
+        self.seed = torch.from_numpy(seeds.view(np.int32).copy()).cuda()
+        self.live = torch.zeros(n, dtype=torch.int32, device="cuda")
+        self.m2 = torch.zeros(n, dtype=torch.float32, device="cuda") if m2 else None
+
+    def host(self):
+        return (self.sums.cpu().numpy(), self.seed.cpu().numpy().view(np.uint32),
+                self.live.cpu().numpy().view(np.uint32))
+
+
+def _resume(device, cam, nx, ny, spp, depth, st, ids=None, begin=0, sync=True):
+    """One pass over st on the torch current stream (ids: a device int64 tensor, else the range from begin)."""
+    import torch
+
+    device.render_resume_device(cam, nx, ny, spp, depth, st.sums.data_ptr(), st.seed.data_ptr(),
+                                live_ptr=st.live.data_ptr(), m2_ptr=st.m2.data_ptr() if st.m2 is not None else 0,
+                                pixel_begin=begin, pixel_count=st.n, pixel_ids_ptr=ids.data_ptr() if ids is not None else 0,
+                                stream=torch.cuda.current_stream().cuda_stream)
+    if sync:
+        torch.cuda.synchronize()
+
+
+def _oneshot(device, cam, nx, ny, spp, depth, ids=None, n=None):
+    """rtp_render_device of the total: device tensors (rgba, seeds, live)."""
+    import torch
+
+    n = nx * ny if n is None else n
+    out = torch.full((n, 4), 7.0, dtype=torch.float32, device="cuda")
+    seeds = torch.zeros(n, dtype=torch.int32, device="cuda")
+    live = torch.zeros(n, dtype=torch.int32, device="cuda")
+    device.render_device(cam, nx, ny, spp, depth, out.data_ptr(), pixel_count=n,
+                         pixel_ids_ptr=ids.data_ptr() if ids is not None else 0,
+                         stream=torch.cuda.current_stream().cuda_stream, seed_ptr=seeds.data_ptr(),
+                         live_ptr=live.data_ptr())
+    torch.cuda.synchronize()
+    return out, seeds, live
+
+
+def _host(t):
+    out, seeds, live = t
+    return out.cpu().numpy(), seeds.cpu().numpy().view(np.uint32), live.cpu().numpy().view(np.uint32)
+
+
+def _split(device, cam, nx, ny, depth, sizes, pixels=None, m2=True):
+    """A fresh whole-canvas (or pixel-list) state resumed once per size."""
+    import torch
+
+    pix = np.arange(nx * ny, dtype=np.int64) if pixels is None else np.asarray(pixels, dtype=np.int64)
+    st = State(pix, m2=m2)
+    ids = torch.from_numpy(pix).cuda() if pixels is not None else None
+    for s in sizes:
+        _resume(device, cam, nx, ny, s, depth, st, ids=ids)
+    return st
+
+
+NX, NY, DEPTH, SPP = 48, 40, 6, 7
+
+
+@pytest.fixture(scope="module")
+def small(device, oracle):
+    """The 48 x 40 case's references, computed once: the one-shot render and the oracle."""
+    device.set_cornell_box(0)
+    pix = np.arange(NX * NY, dtype=np.int64)
+    return dict(oneshot=_host(_oneshot(device, _cam(), NX, NY, SPP, DEPTH)),
+                oracle=oracle.render_pixels(oracle.cornell_box(0), _oracle_cam(oracle, NX, NY, _cam()), NX, NY, SPP,
+                                            DEPTH, pix))
+
+
+# 1. the plain instance
+@pytest.mark.parametrize("sizes", [(3, 4), (1,) * 7, (0, 7, 0)], ids=["3+4", "7x1", "0+7+0"])
+def test_split_equals_oneshot_and_oracle(device, small, sizes):
+    assert _plan_steal(NX * NY) == 0
+    device.set_cornell_box(0)
+    got = _split(device, _cam(), NX, NY, DEPTH, sizes).host()
+    assert_render_equal(got, small["oneshot"], f"split {sizes} vs rtp_render_device({SPP})")
+    assert_render_equal(got, small["oracle"], f"split {sizes} vs the oracle")
+
+
+def test_split_at_depth_50(device, oracle):
+    """Most samples end long before depth 50: the fast-forward over their dead
+    depths runs on both sides of the pass boundary."""
+    device.set_cornell_box(0)
+    got = _split(device, _cam(), NX, NY, 50, (2, 3)).host()
+    want = oracle.render_pixels(oracle.cornell_box(0), _oracle_cam(oracle, NX, NY, _cam()), NX, NY, 5, 50,
+                                np.arange(NX * NY, dtype=np.int64))
+    assert_render_equal(got, want, "depth 50, 2+3 vs the oracle")
+
+
+# 2. the arrays of an ordinary render are a state
+def test_render_then_resume(device, small):
+    device.set_cornell_box(0)
+    out, seeds, live = _oneshot(device, _cam(), NX, NY, 3, DEPTH)
+    st = State(np.arange(NX * NY), m2=False)
+    st.sums, st.seed, st.live = out, seeds, live
+    _resume(device, _cam(), NX, NY, 4, DEPTH, st)
+    assert_render_equal(st.host(), small["oneshot"], "render_device(3) + resume(4)")
+
+
+def test_host_entry_point(device, small):
+    """rtp_render_resume (host arrays): 3 + 4 over the whole canvas, and over a pixel list."""
+    device.set_cornell_box(0)
+    n = NX * NY
+    rgba, seed = np.zeros((n, 4), np.float32), np.arange(n, dtype=np.uint32)
+    live, m2 = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+    for s in (3, 4):
+        st = device.render_resume(_cam(), NX, NY, s, DEPTH, rgba, seed, live, m2)
+        assert st.samples == n * s
+    assert_render_equal((rgba, seed, live), small["oneshot"], "rtp_render_resume 3+4")
+    ids = np.array([5, 1900, 77], dtype=np.int64)
+    r2, s2 = np.zeros((3, 4), np.float32), ids.astype(np.uint32)
+    device.render_resume(_cam(), NX, NY, SPP, DEPTH, r2, s2, pixels=ids)
+    assert_render_equal((r2, s2, None), tuple(a[ids] for a in small["oneshot"]), "rtp_render_resume pixel list")
+
+
+# 3. a pixel list
+def test_pixel_list(device, oracle, small):
+    device.set_cornell_box(0)
+    ids = np.random.default_rng(11).permutation(NX * NY)[:300].astype(np.int64)
+    assert np.unique(ids).size == 300 and not np.all(np.diff(ids) > 0)
+    got = _split(device, _cam(), NX, NY, DEPTH, (2, 5), pixels=ids).host()
+    rgba, seeds, live, _ = device.render_pixels(_cam(), NX, NY, SPP, DEPTH, ids)
+    assert_render_equal(got, (rgba, seeds, live), "pixel list 2+5 vs rtp_render_pixels(7)")
+    assert_render_equal(got, tuple(a[ids] for a in small["oracle"]), "pixel list 2+5 vs the oracle")
+
+
+# 4. the stealing instance
+def test_stealing(device, oracle):
+    nx, ny, depth = 1920, 1080, 50
+    n = nx * ny
+    assert _plan_steal(n) > 0, "the launch must be large enough to steal"
+    device.set_cornell_box(0)
+    got = _split(device, _cam(), nx, ny, depth, (2, 2)).host()
+    assert_render_equal(got, _host(_oneshot(device, _cam(), nx, ny, 4, depth)), "stolen 2+2 vs rtp_render_device(4)")
+    pix = np.unique(np.r_[np.arange(32), np.arange(n - 64, n),
+                          np.random.default_rng(5).choice(n, 192, replace=False)]).astype(np.int64)
+    want = oracle.render_pixels(oracle.cornell_box(0), _oracle_cam(oracle, nx, ny, _cam()), nx, ny, 4, depth, pix)
+    assert_render_equal(tuple(a[pix] for a in got), want, "stolen 2+2 vs the oracle")
+
+
+# 5. the sphere BVH (global walk), without and with stealing, and a scene set for the LDS walk
+@pytest.fixture
+def spheres(device):
+    device.set_cornell_box(3)
+    yield
+    device.set_cornell_box(0)
+
+
+def _bvh_case(device, oracle, nx, ny, sizes, what):
+    total, depth, n = sum(sizes), 50, nx * ny
+    got = _split(device, _cam(), nx, ny, depth, sizes).host()
+    assert_render_equal(got, _host(_oneshot(device, _cam(), nx, ny, total, depth)), f"{what} vs rtp_render_device")
+    pix = np.sort(np.random.default_rng(7).choice(n, 128, replace=False)).astype(np.int64)
+    want = oracle.render_pixels(oracle.cornell_box(3), _oracle_cam(oracle, nx, ny, _cam()), nx, ny, total, depth, pix)
+    assert_render_equal(tuple(a[pix] for a in got), want, f"{what} vs the oracle")
+    return got
+
+
+def test_sphere_bvh(device, oracle, spheres, monkeypatch):
+    assert device.sphere_walk() == "global" and _plan_steal(128 * 128, 1) == 0
+    plain = _bvh_case(device, oracle, 128, 128, (1, 2), "1000 spheres 1+2")
+    monkeypatch.setenv("RTP_BVH_LDS", "1")
+    device.set_cornell_box(3)
+    monkeypatch.delenv("RTP_BVH_LDS")
+    assert device.sphere_walk() == "lds"
+    lds = _split(device, _cam(), 128, 128, 50, (1, 2)).host()
+    assert_render_equal(lds, plain, "a scene set for the LDS walk resumes through the global walk")
+
+
+def test_sphere_bvh_stealing(device, oracle, spheres):
+    assert _plan_steal(1024 * 1024, 1) > 0, "the launch must be large enough to steal"
+    _bvh_case(device, oracle, 1024, 1024, (1, 1), "1000 spheres stolen 1+1")
+
+
+# 6. m2
+def test_m2_equals_oracle_samples(device, oracle):
+    nx, ny, depth, sizes = 32, 24, 6, (2, 3)
+    ids = np.linspace(0, nx * ny - 1, 64).astype(np.int64)
+    assert np.unique(ids).size == 64
+    device.set_cornell_box(0)
+    st = _split(device, _cam(), nx, ny, depth, sizes, pixels=ids)
+    got_m2 = st.m2.cpu().numpy()
+    # the oracle's samples one at a time: sample i of pixel p starts from the
+    # state the previous one left, seed_base + p = state
+    sc, ocam = oracle.cornell_box(0), _oracle_cam(oracle, nx, ny, _cam())
+    f = np.float32
+    want_m2, want_sums, want_seed = np.zeros(64, np.float32), np.zeros((64, 3), np.float32), np.zeros(64, np.uint32)
+    for k, p in enumerate(ids.tolist()):
+        state, m2, sums = p, f(0), np.zeros(3, np.float32)
+        for _ in range(sum(sizes)):
+            rgba, seeds, _live = oracle.render_pixels(sc, ocam, nx, ny, 1, depth, [p],
+                                                      seed_base=(state - p) & 0xFFFFFFFF, nthreads=1)
+            c = rgba[0, :3].astype(np.float32)
+            y = f(f(f(f(0.2126) * c[0]) + f(f(0.7152) * c[1])) + f(f(0.0722) * c[2]))
+            m2 = f(m2 + f(y * y))
+            sums = sums + c
+            state = int(seeds[0])
+        want_m2[k], want_sums[k], want_seed[k] = m2, sums, state
+    rgba, seed, live = st.host()
+    assert same_bits_or_both_nan(rgba[:, :3], want_sums).all(), "the chained oracle samples do not add up to the sums"
+    assert np.array_equal(seed, want_seed)
+    bad = np.flatnonzero(~same_bits_or_both_nan(got_m2, want_m2))
+    assert bad.size == 0, f"m2 differs at {bad[:8].tolist()}: got {got_m2[bad[:4]]}, want {want_m2[bad[:4]]}"
+    assert (got_m2[np.isfinite(got_m2)] >= 0).all() and got_m2.max() > 0
+    # passing m2 changes nothing else
+    without = _split(device, _cam(), nx, ny, depth, sizes, pixels=ids, m2=False).host()
+    assert_render_equal(without, (rgba, seed, live), "m2 = NULL")
+
+
+# 7. stream order
+def test_passes_chain_without_synchronising(device, small):
+    import torch
+
+    device.set_cornell_box(0)
+    st = State(np.arange(NX * NY))
+    for s in (2, 4, 1):
+        _resume(device, _cam(), NX, NY, s, DEPTH, st, sync=False)
+    torch.cuda.synchronize()
+    assert_render_equal(st.host(), small["oneshot"], "2+4+1 queued back to back")
+
+
+def test_two_states_back_to_back(device, small):
+    import torch
+
+    device.set_cornell_box(0)
+    a, b = State(np.arange(NX * NY)), State(np.arange(NX * NY))
+    for s in (3, 4):
+        _resume(device, _cam(), NX, NY, s, DEPTH, a, sync=False)
+        _resume(device, _other_cam(), NX, NY, s, DEPTH, b, sync=False)
+    torch.cuda.synchronize()
+    assert_render_equal(a.host(), small["oneshot"], "state of the default camera")
+    assert_render_equal(b.host(), _host(_oneshot(device, _other_cam(), NX, NY, SPP, DEPTH)), "state of the other camera")
+
+
+# 8. errors launch nothing
+def test_errors_leave_the_state_untouched(device, monkeypatch):
+    import torch
+
+    from raytracingtherestofyourlife_amd import _lib
+
+    L = _lib.load()
+    n = NX * NY
+    device.set_cornell_box(0)
+    sums = torch.full((n, 4), -5.0, dtype=torch.float32, device="cuda")
+    seed = torch.full((n,), 12345, dtype=torch.int32, device="cuda")
+    live = torch.full((n,), 77, dtype=torch.int32, device="cuda")
+    m2 = torch.full((n,), -3.0, dtype=torch.float32, device="cuda")
+    cam = _cam().to_c()
+    p = lambda t: ctypes.cast(t.data_ptr(), ctypes.POINTER(ctypes.c_float if t.dtype == torch.float32 else ctypes.c_uint32))
+    full = _lib.RtpRenderState(p(sums), p(seed), p(live), p(m2))
+
+    def call(state, begin=0, count=n, env=None):
+        for k, v in (env or {}).items():
+            monkeypatch.setenv(k, v)
+        rc = L.rtp_render_resume_device(device.handle, ctypes.byref(cam), NX, NY, 2, DEPTH, begin, count, None,
+                                        ctypes.byref(state) if state is not None else None, None, None)
+        torch.cuda.synchronize()
+        for k in env or {}:
+            monkeypatch.delenv(k)
+        return rc
+
+    cases = [("NULL seed", dict(state=_lib.RtpRenderState(p(sums), None, p(live), p(m2)))),
+             ("NULL rgba", dict(state=_lib.RtpRenderState(None, p(seed), None, None))),
+             ("NULL state", dict(state=None)),
+             ("RTP_KERNEL=1", dict(state=full, env={"RTP_KERNEL": "1"})),
+             ("RTP_DEBUG_STATS=1", dict(state=full, env={"RTP_DEBUG_STATS": "1"})),
+             ("range past the canvas", dict(state=full, begin=1, count=n)),
+             ("negative begin", dict(state=full, begin=-1, count=4))]
+    for what, kw in cases:
+        assert call(**kw) == _lib.RTP_ERR_INVALID_ARGUMENT, what
+        assert L.rtp_last_error(), what
+        assert bool((sums == -5.0).all()) and bool((seed == 12345).all()), what
+        assert bool((live == 77).all()) and bool((m2 == -3.0).all()), what
+    # spp = 0 is no error and no change
+    rc = L.rtp_render_resume_device(device.handle, ctypes.byref(cam), NX, NY, 0, DEPTH, 0, n, None, ctypes.byref(full),
+                                    None, None)
+    torch.cuda.synchronize()
+    assert rc == _lib.RTP_OK and bool((sums == -5.0).all()) and bool((seed == 12345).all())
+
+
+# 9. ProgressiveRender
+def test_progressive_render_refines_and_checkpoints(device, tmp_path):
+    import raytracingtherestofyourlife_amd as rtp
+
+    nx, ny, depth = 64, 48, 6
+    n = nx * ny
+    device.set_cornell_box(0)
+    r = rtp.ProgressiveRender(device, _cam(), nx, ny, depth)
+    r.step(4)
+    noise = r.noise()
+    assert noise.shape == (n,)
+    threshold = float(np.median(noise))
+    active = [r.refine(4, threshold, max_spp=16) for _ in range(3)]
+    assert 0 < active[0] < n, active
+    s = r.state()
+    counts = np.unique(s["count"])
+    assert counts.min() == 4 and counts.max() <= 16 and counts.size > 1, counts
+    for c in counts.tolist():
+        pix = np.flatnonzero(s["count"] == c).astype(np.int64)
+        rgba, seeds, live, _ = device.render_pixels(_cam(), nx, ny, c, depth, pix)
+        assert_render_equal((s["sums"][pix], s["seed"][pix], s["live"][pix]), (rgba, seeds, live),
+                            f"the {pix.size} pixels with {c} samples vs rtp_render_pixels({c})")
+    # image(): NormalizeFunctor with the per-pixel count
+    img = r.image()
+    for c in counts.tolist():
+        pix = np.flatnonzero(s["count"] == c)
+        want = rtp.normalize(np.ascontiguousarray(s["sums"][pix]), c)
+        assert same_bits_or_both_nan(img[pix], want).all()
+    # a loaded checkpoint continues like the render it was saved from
+    path = str(tmp_path / "ck.npz")
+    r.save(path)
+    r2 = rtp.ProgressiveRender.load(device, path)
+    some = np.arange(0, n, 3, dtype=np.int64)
+    for x in (r, r2):
+        x.step(2)
+        x.step(1, active=some)
+    a, b = r.state(), r2.state()
+    assert_render_equal((a["sums"], a["seed"], a["live"]), (b["sums"], b["seed"], b["live"]), "loaded vs continued")
+    assert same_bits_or_both_nan(a["m2"], b["m2"]).all() and np.array_equal(a["count"], b["count"])
+    assert np.array_equal(a["count"], s["count"] + 2 + np.isin(np.arange(n), some))
+
+
+def test_run_path_progressive_equals_run_path(device):
+    import raytracingtherestofyourlife_amd as rtp
+
+    nx, ny, spp, depth = 64, 48, 10, 6
+    cb = rtp.CornellBox()
+    cb.buildDataSet()
+    one, prog = rtp.CanvasRayTracer(nx, ny), rtp.CanvasRayTracer(nx, ny)
+    rtp.runPath(nx, ny, spp, depth, one, _cam(), cb, device=device)
+    seen = []
+    r = rtp.runPathProgressive(nx, ny, spp, depth, prog, _cam(), cb, passes=3, device=device,
+                               on_pass=lambda i, render: seen.append(int(render.count.max())))
+    assert seen == [4, 7, 10] and int(r.count.min()) == spp
+    assert same_bits_or_both_nan(prog.GetColorBuffer(), one.GetColorBuffer()).all()
+    device.set_cornell_box(0)
+
+
+# 10. the driver
+def test_rtp_path_passes_write_the_same_files(tmp_path):
+    exe = os.path.join(ROOT, "examples", "rtp_path")
+    base = [exe, "-x", "64", "-y", "48", "-samplecount", "9", "-raydepth", "5", "-raw", "r"]
+    files = {}
+    for name, extra in (("oneshot", []), ("passes", ["-passes", "4", "-preview"])):
+        d = tmp_path / name
+        d.mkdir()
+        res = subprocess.run(base + extra, cwd=d, capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr
+        files[name] = {f: (d / f).read_bytes() for f in sorted(os.listdir(d))}
+    assert sorted(files["oneshot"]) == ["output.pnm", "r"]
+    previews = [f"output-pass{i}.pnm" for i in (1, 2, 3, 4)]
+    assert sorted(files["passes"]) == sorted(["output.pnm", "r"] + previews)
+    for f in ("output.pnm", "r"):
+        assert files["passes"][f] == files["oneshot"][f], f"{f} differs from the run without -passes"
+    assert files["passes"]["output-pass4.pnm"] == files["oneshot"]["output.pnm"]
+    assert files["passes"]["output-pass1.pnm"] != files["oneshot"]["output.pnm"]

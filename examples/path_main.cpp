@@ -7,7 +7,7 @@
 //            [-hemisphere [-phicount 15] [-thetacount 15]]
 //            [-o output] [-raw prefix] [-variant 0] [-device 0]
 //            [-rank 0 -world 1] [-dry-run] [-viewbatch N]
-//            [-passes N [-preview]]
+//            [-passes N [-preview]] [-denoise [-levels N]]
 //
 // Writes <o>.pnm like main.cc, or <o>-<phi>-<theta>.pnm per hemisphere view
 // (generate(), "%.4f" formatting).  -raw additionally dumps the normalised
@@ -26,6 +26,13 @@
 // each pass: the image of the samples so far.  With -dry-run the pass sizes
 // are printed, one line, and nothing is rendered.  -passes with -hemisphere or
 // -direct, or N < 1, is an error (exit code 2).
+// -denoise: also writes <o>-denoised.pnm, the denoised preview of the finished
+// render (rtp::ProgressiveRender::Denoised: first-hit guides and an a-trous
+// filter of -levels N levels, default 5), and with -preview
+// <o>-pass<i>-denoised.pnm after each pass; the render goes through the
+// resumable passes (one pass without -passes) and every other file keeps its
+// bytes.  -denoise with -hemisphere or -direct, or -levels outside 1..8, is an
+// error (exit code 2).
 // -direct: the quad mappers' one-bounce AOVs (main.cc:623-651, generate()
 // :399-420): direct.pnm, depth.pnm, normals.pnm, albedo.pnm (or
 // direct-<phi>-<theta>.pnm ... per hemisphere view), all four from one launch.
@@ -83,7 +90,8 @@ int main(int argc, char** argv) {
   int x = 128, y = 128, s = 10, depth = 5, variant = 0, device = 0;  // main.cc:56-62 defaults
   int phiCount = 15, thetaCount = 15, rank = 0, world = 1, viewBatch = -1;
   bool hemi = false, dry = false, direct = false, preview = false, havePasses = false;
-  int passes = 1;
+  int passes = 1, levels = 5;
+  bool denoise = false;
   std::string out = "output", raw;
   for (int i = 1; i < argc; i++) {
     auto next = [&](const char* flag) -> const char* {
@@ -105,6 +113,8 @@ int main(int argc, char** argv) {
     else if ((v = next("-world"))) world = std::atoi(v);
     else if ((v = next("-viewbatch"))) viewBatch = std::atoi(v);
     else if ((v = next("-passes"))) passes = std::atoi(v), havePasses = true;
+    else if ((v = next("-levels"))) levels = std::atoi(v);
+    else if (!std::strcmp(argv[i], "-denoise")) denoise = true;
     else if (!std::strcmp(argv[i], "-preview")) preview = true;
     else if (!std::strcmp(argv[i], "-hemisphere")) hemi = true;
     else if (!std::strcmp(argv[i], "-dry-run")) dry = true;
@@ -116,6 +126,11 @@ int main(int argc, char** argv) {
   }
   if (havePasses && (passes < 1 || hemi || direct)) {
     std::cerr << "rtp_path: -passes needs N >= 1 and renders the single view (no -hemisphere, no -direct)"
+              << std::endl;
+    return 2;
+  }
+  if (denoise && (hemi || direct || levels < 1 || levels > 8)) {
+    std::cerr << "rtp_path: -denoise renders the single view (no -hemisphere, no -direct) with -levels 1..8"
               << std::endl;
     return 2;
   }
@@ -164,9 +179,15 @@ int main(int argc, char** argv) {
         rtp::SavePNM("albedo" + suffix + ".pnm", b.albedo, x, y);
         return;
       }
-      if (havePasses) {
-        rtp::runPathProgressive(x, y, s, depth, canvas, cam, cb, passes, dev, [&](int i) {
-          if (preview) rtp::SavePNM(out + "-pass" + std::to_string(i + 1) + ".pnm", canvas);
+      if (havePasses || denoise) {
+        rtp_denoise_params prm = rtp::ProgressiveRender::DefaultDenoiseParams();
+        prm.levels = levels;
+        rtp::runPathProgressiveRender(x, y, s, depth, canvas, cam, cb, passes, dev,
+                                      [&](int i, rtp::ProgressiveRender& r) {
+          const std::string pass = out + "-pass" + std::to_string(i + 1);
+          if (preview) rtp::SavePNM(pass + ".pnm", canvas);
+          if (preview && denoise) rtp::SavePNM(pass + "-denoised.pnm", r.Denoised(prm), x, y);
+          if (denoise && i + 1 == passes) rtp::SavePNM(out + suffix + "-denoised.pnm", r.Denoised(prm), x, y);
         });
       } else {
         rtp::runPath(x, y, s, depth, canvas, cam, cb, dev);

@@ -253,6 +253,94 @@ rtp_status rtp_render_resume(rtp_context* ctx, const rtp_camera* cam, int32_t nx
                              int32_t depth, const int64_t* pixel_ids, int64_t pixel_count,
                              const rtp_render_state* host_state, rtp_stats* stats);
 
+/* ------------------------------------------------------------------------
+ * Denoised previews: first-hit guides, resolve, and an a-trous filter.  A
+ * low-spp render state becomes a clean preview without leaving the device:
+ *   guides   what the path camera sees first at each pixel centre,
+ *   resolve  state -> mean radiance and the variance of the mean,
+ *   denoise  a variance-guided, edge-avoiding a-trous wavelet filter (Dammertz
+ *            et al. 2010; the spatial filter of SVGF).
+ * All arithmetic below is float, in the order written, without contraction;
+ * the results are these bits.
+ *
+ * Guides.  The ray of pixel (i, j) is the path camera's ray (Camera::RayGen)
+ * with both jitter draws replaced by 0.5f: no RNG is touched, no render state
+ * read.  The closest hit is the path kernel's own (same tmin, same tie order;
+ * quads, spheres, and the sphere BVH when the scene has one).  Outputs, device
+ * buffers of nx*ny entries, each nullable (at least one non-NULL):
+ *   g0   float4: the unit geometric normal the path shades that hit with (the
+ *        stored quad normal, or (hp - c) / r for a sphere), flipped to face
+ *        the ray origin, and t.  Miss: (0, 0, 0, +inf).
+ *   g1   float4: tex_rgb of the hit primitive's texture (every material type)
+ *        and 1.  Miss: zeros.
+ *   prim int32: kind * 2^24 + index as rtp_debug_closest_hit reports them
+ *        (kind 0 quad, 1 sphere).  Miss: -1.
+ * Asynchronous on hip_stream; stats != NULL synchronises (kernel_ms).
+ * RTP_ERR_INVALID_ARGUMENT / RTP_ERR_NO_SCENE, nothing launched: a NULL
+ * camera, a bad size or field of view, every output NULL, no scene set. */
+rtp_status rtp_render_guides_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, float* d_g0,
+                                    float* d_g1, int32_t* d_prim, void* hip_stream, rtp_stats* stats);
+/* Host buffers, synchronous. */
+rtp_status rtp_render_guides(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, float* g0, float* g1,
+                             int32_t* prim, rtp_stats* stats);
+
+/* Resolve.  d_sums: float4[n] running rgb sums; d_m2: float[n], nullable;
+ * d_count: int32[n] samples per entry, nullable (then every entry has spp).
+ * d_cv: float4[n] = mean r, g, b and var.  With nf = (float)count:
+ *   invalid entry (count <= 0, a non-finite rgb sum, or m2 given and
+ *   non-finite): (0, 0, 0, -1).  A negative var marks an invalid pixel below.
+ *   otherwise rgb = sums / nf; Y = (0.2126f*sx + 0.7152f*sy) + 0.0722f*sz;
+ *   l = Y / nf; var = l*l when count == 1 or m2 is NULL, else
+ *   spread = m2 - (Y*Y)/nf; var = ((spread > 0 ? spread : 0) / (nf - 1.f)) / nf.
+ * Asynchronous; stats != NULL synchronises. */
+rtp_status rtp_resolve_device(rtp_context* ctx, const float* d_sums, const float* d_m2, const int32_t* d_count,
+                              int32_t spp, int64_t n, float* d_cv, void* hip_stream, rtp_stats* stats);
+/* Host buffers, synchronous. */
+rtp_status rtp_resolve(rtp_context* ctx, const float* sums, const float* m2, const int32_t* count, int32_t spp,
+                       int64_t n, float* cv, rtp_stats* stats);
+
+typedef struct {
+  int32_t levels;             /* L, 1..8: level s = 0..L-1 has step = 1 << s */
+  float sigma_l;              /* luminance, in standard deviations of the centre's mean; > 0 */
+  float sigma_z;              /* depth (t) difference per pixel of step; > 0 */
+  float sigma_a;              /* albedo distance; > 0 */
+  int32_t normal_log2;        /* 0..8: the normal weight is max(0, n_p.n_q)^(2^normal_log2) */
+} rtp_denoise_params;
+
+/* The filter.  d_cv: float4[nx*ny] from resolve (not written); d_g0, d_g1:
+ * the guides, NULL as a pair (then only the luminance term acts); d_out and
+ * d_scratch: float4[nx*ny] each, aliasing neither an input nor each other.
+ * The L levels ping-pong between d_scratch and d_out, the last into d_out.
+ * Level s, step = 1 << s, for pixel p with input (c_p, var_p):
+ *   taps q = p + step*(dx, dy), dy = -2..2 outer, dx = -2..2 inner, with
+ *   k = h[dx+2]*h[dy+2], h = {1/16, 1/4, 3/8, 1/4, 1/16}; a tap outside the
+ *   canvas or with var_q < 0 is skipped.
+ *   centre tap: w = 9/64 when var_p >= 0, skipped otherwise.
+ *   other taps: l_x = (0.2126f*r + 0.7152f*g) + 0.0722f*b;
+ *     wl = 1 when p is invalid, else dl = fabsf(l_p - l_q) / (sigma_l *
+ *       sqrtf(var_p) + 1e-4f), wl = 1.f / (1.f + dl*dl);
+ *     without guides wn = wz = wa = 1; with guides: hit flags (g1.w) that
+ *     differ give w = 0; both a miss wn = wz = wa = 1; both a hit
+ *       m = max(0.f, (nx_p*nx_q + ny_p*ny_q) + nz_p*nz_q), wn = m squared
+ *         normal_log2 times;
+ *       dz = fabsf(t_p - t_q) / (sigma_z * (float)step), wz = 1.f/(1.f + dz*dz);
+ *       da = (ax*ax + ay*ay) + az*az over the albedo differences,
+ *         wa = 1.f / (1.f + da / (sigma_a*sigma_a));
+ *     w = (((k*wn)*wz)*wa)*wl.
+ *   in tap order: sc += w*c_q per channel, sv += (w*w)*var_q, sw += w.
+ *   result (sc/sw, sv/(sw*sw)) when sw > 0, else the level's input pixel.
+ * An invalid pixel with valid neighbours is filled from them; it never
+ * spreads.  Asynchronous; stats != NULL synchronises (kernel_ms: all levels).
+ * RTP_ERR_INVALID_ARGUMENT, nothing launched: a NULL d_cv, d_out, d_scratch
+ * or params, a bad size, levels outside 1..8, a sigma not above 0,
+ * normal_log2 outside 0..8, one guide without the other, aliased buffers. */
+rtp_status rtp_denoise_device(rtp_context* ctx, const float* d_cv, const float* d_g0, const float* d_g1, int32_t nx,
+                              int32_t ny, const rtp_denoise_params* params, float* d_out, float* d_scratch,
+                              void* hip_stream, rtp_stats* stats);
+/* Host buffers, synchronous (the scratch is the library's). */
+rtp_status rtp_denoise(rtp_context* ctx, const float* cv, const float* g0, const float* g1, int32_t nx, int32_t ny,
+                       const rtp_denoise_params* params, float* out, rtp_stats* stats);
+
 /* Host-side helpers of the application layer (main.cc). */
 rtp_status rtp_normalize(float* rgba, int64_t n_pixels, int32_t spp);
 rtp_status rtp_write_pnm(const char* path, const float* rgba, int32_t nx, int32_t ny);

@@ -192,6 +192,44 @@ class Device {
                             (int64_t)n, &st, stats));
   }
 
+  // rtp_render_guides: what the path camera sees first at each pixel centre
+  // of the current scene (include/rtp.h): g0 = normal facing the ray and t,
+  // g1 = texture colour and hit flag, prim = kind << 24 | index (-1: a miss).
+  struct Guides {
+    std::vector<Vec4f> g0, g1;
+    std::vector<int32_t> prim;
+  };
+  Guides RenderGuides(const rtp_camera& camera, int nx, int ny, rtp_stats* stats = nullptr) const {
+    if (nx <= 0 || ny <= 0) throw ErrorBadValue("Camera width/height must be greater than zero.");
+    const size_t n = (size_t)nx * (size_t)ny;
+    Guides g{std::vector<Vec4f>(n), std::vector<Vec4f>(n), std::vector<int32_t>(n)};
+    Check(rtp_render_guides(get(), &camera, nx, ny, g.g0.data()->data(), g.g1.data()->data(), g.prim.data(), stats));
+    return g;
+  }
+
+  // rtp_resolve: running sums (and m2, nullable) of `samplecount` samples per
+  // pixel -> mean rgb and the variance of the mean (w < 0: an invalid pixel).
+  std::vector<Vec4f> Resolve(const std::vector<Vec4f>& sums, const std::vector<float>* m2, int samplecount) const {
+    if (sums.empty() || (m2 && m2->size() != sums.size()))
+      throw ErrorBadValue("Resolve: the state arrays must have one entry per pixel");
+    std::vector<Vec4f> cv(sums.size());
+    Check(rtp_resolve(get(), sums.data()->data(), m2 ? m2->data() : nullptr, nullptr, samplecount,
+                      (int64_t)sums.size(), cv.data()->data(), nullptr));
+    return cv;
+  }
+
+  // rtp_denoise: the a-trous filter over a resolved canvas; guides nullable.
+  std::vector<Vec4f> Denoise(const std::vector<Vec4f>& cv, const Guides* guides, int nx, int ny,
+                             const rtp_denoise_params& params, rtp_stats* stats = nullptr) const {
+    if (nx <= 0 || ny <= 0 || cv.size() != (size_t)nx * (size_t)ny ||
+        (guides && (guides->g0.size() != cv.size() || guides->g1.size() != cv.size())))
+      throw ErrorBadValue("Denoise: the buffers must have nx * ny entries");
+    std::vector<Vec4f> out(cv.size());
+    Check(rtp_denoise(get(), cv.data()->data(), guides ? guides->g0.data()->data() : nullptr,
+                      guides ? guides->g1.data()->data() : nullptr, nx, ny, &params, out.data()->data(), stats));
+    return out;
+  }
+
  private:
   std::shared_ptr<rtp_context> ctx_;
 };
@@ -821,6 +859,32 @@ class ProgressiveRender {
     canvas.GetColorBuffer().assign(sums_.begin(), sums_.end());
     Normalize(canvas.GetColorBuffer(), (int)samples_);
   }
+  // The denoised preview of the samples so far: resolve, the first-hit guides
+  // (rendered once and kept) and the a-trous filter (include/rtp.h), then
+  // sqrt of the rgb like Canvas(); w = the filtered variance.  A sigma_z <= 0
+  // in params means the default: the camera's distance to its look-at point
+  // spread over the canvas rows, |look_at - position| / ny.  The Python ProgressiveRender
+  // .denoised gives the same bytes for the same parameters.
+  std::vector<Vec4f> Denoised(rtp_denoise_params params = DefaultDenoiseParams()) {
+    if (samples_ > INT32_MAX) throw ErrorBadValue("ProgressiveRender::Denoised: more than 2^31-1 samples");
+    if (!have_guides_) {
+      guides_ = device_->RenderGuides(cam_, nx_, ny_);
+      have_guides_ = true;
+    }
+    if (!(params.sigma_z > 0.f)) {
+      double d[3];
+      for (int k = 0; k < 3; k++) d[k] = (double)cam_.look_at[k] - (double)cam_.position[k];
+      const double dist = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+      params.sigma_z = dist > 0 ? (float)(dist / ny_) : 1.0f;
+    }
+    std::vector<Vec4f> out = device_->Denoise(device_->Resolve(sums_, &m2_, (int)samples_), &guides_, nx_, ny_, params);
+    for (Vec4f& c : out)
+      for (int k = 0; k < 3; k++) c[k] = std::sqrt(c[k]);
+    return out;
+  }
+  // ProgressiveRender.denoised's defaults: 5 levels, sigma_l 4, sigma_z 0 (the
+  // default above), sigma_a 0.1, normal_log2 5
+  static rtp_denoise_params DefaultDenoiseParams() { return rtp_denoise_params{5, 4.0f, 0.0f, 0.1f, 5}; }
   const std::vector<Vec4f>& Sums() const { return sums_; }
   const std::vector<uint32_t>& Seeds() const { return seed_; }
   const std::vector<uint32_t>& LiveBounces() const { return live_; }
@@ -834,15 +898,19 @@ class ProgressiveRender {
   std::vector<Vec4f> sums_;
   std::vector<uint32_t> seed_, live_;
   std::vector<float> m2_;
+  Device::Guides guides_;  // Denoised(): rendered on first use
+  bool have_guides_ = false;
 };
 
 // runPath rendered in `passes` passes (SplitPasses): the canvas ends with
 // runPath's colours, bit for bit.  on_pass(i), when given, is called after
 // pass i with the canvas holding the normalised image so far (a preview).
+// runPathProgressiveRender hands on_pass(i, render) the ProgressiveRender too
+// (its Denoised() is the denoised preview of that pass).
 template <class OnPass>
-inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, rendering::CanvasRayTracer& canvas,
-                               rendering::Camera& cam, CornellBox& cb, int passes, std::shared_ptr<Device> device,
-                               OnPass on_pass) {
+inline void runPathProgressiveRender(int nx, int ny, int samplecount, int depthcount,
+                                     rendering::CanvasRayTracer& canvas, rendering::Camera& cam, CornellBox& cb,
+                                     int passes, std::shared_ptr<Device> device, OnPass on_pass) {
   const std::vector<int> sizes = SplitPasses(samplecount, passes);
   rendering::MapperPathTracer mapper(samplecount, depthcount, cb.matIdx, cb.texIdx, cb.matType, cb.texType, cb.tex,
                                      std::move(device));
@@ -851,8 +919,15 @@ inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, 
   for (size_t i = 0; i < sizes.size(); i++) {
     render.Step(sizes[i]);
     render.Canvas(canvas);
-    on_pass((int)i);
+    on_pass((int)i, render);
   }
+}
+template <class OnPass>
+inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, rendering::CanvasRayTracer& canvas,
+                               rendering::Camera& cam, CornellBox& cb, int passes, std::shared_ptr<Device> device,
+                               OnPass on_pass) {
+  runPathProgressiveRender(nx, ny, samplecount, depthcount, canvas, cam, cb, passes, std::move(device),
+                           [&](int i, ProgressiveRender&) { on_pass(i); });
 }
 inline void runPathProgressive(int nx, int ny, int samplecount, int depthcount, rendering::CanvasRayTracer& canvas,
                                rendering::Camera& cam, CornellBox& cb, int passes,

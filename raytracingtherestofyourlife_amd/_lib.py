@@ -67,6 +67,11 @@ class RtpDirectDesc(ctypes.Structure):
                 ("color_map_size", ctypes.c_int32)]
 
 
+class RtpDenoiseParams(ctypes.Structure):
+    _fields_ = [("levels", ctypes.c_int32), ("sigma_l", ctypes.c_float), ("sigma_z", ctypes.c_float),
+                ("sigma_a", ctypes.c_float), ("normal_log2", ctypes.c_int32)]
+
+
 RTP_AOV_COLOR, RTP_AOV_NORMALS, RTP_AOV_ALBEDO = 1, 2, 4
 RTP_FF_TABLES_AUTO, RTP_FF_TABLES_OFF, RTP_FF_TABLES_ON = 0, 1, 2
 
@@ -86,6 +91,8 @@ EXPORTED_SYMBOLS = [
     "rtp_cornell_point_field", "rtp_write_pnm_depth", "rtp_eval_powf", "rtp_set_ff_tables", "rtp_get_ff_tables",
     "rtp_render_planned_device", "rtp_sphere_walk", "rtp_sphere_walk_oct_mask",
     "rtp_render_views_device", "rtp_render_views", "rtp_render_resume_device", "rtp_render_resume",
+    "rtp_render_guides_device", "rtp_render_guides", "rtp_resolve_device", "rtp_resolve", "rtp_denoise_device",
+    "rtp_denoise",
 ]
 
 
@@ -183,6 +190,20 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
                                               ctypes.POINTER(RtpPixelAux), vp, ctypes.POINTER(RtpStats)]
         L.rtp_render_views.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_int32, ctypes.c_int32, f32p, ctypes.POINTER(RtpStats)]
+    # (likewise a revision before the denoised previews)
+    if bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_denoise_device"):
+        skip += ("rtp_render_guides_device", "rtp_render_guides", "rtp_resolve_device", "rtp_resolve",
+                 "rtp_denoise_device", "rtp_denoise")
+    else:
+        stp, dpp = ctypes.POINTER(RtpStats), ctypes.POINTER(RtpDenoiseParams)
+        L.rtp_render_guides_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32, vp, vp,
+                                               vp, vp, stp]
+        L.rtp_render_guides.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32, f32p, f32p,
+                                        i32p, stp]
+        L.rtp_resolve_device.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int64, vp, vp, stp]
+        L.rtp_resolve.argtypes = [vp, f32p, f32p, i32p, ctypes.c_int32, ctypes.c_int64, f32p, stp]
+        L.rtp_denoise_device.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dpp, vp, vp, vp, stp]
+        L.rtp_denoise.argtypes = [vp, f32p, f32p, f32p, ctypes.c_int32, ctypes.c_int32, dpp, f32p, stp]
     L.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
     L.rtp_get_ff_tables.argtypes = [vp, ctypes.POINTER(RtpFfInfo)]
     L.rtp_sphere_walk.argtypes = [vp]

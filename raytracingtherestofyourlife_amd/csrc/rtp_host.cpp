@@ -37,6 +37,8 @@ extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, fl
                                         rtp::DevSphereG* d_geom, hipStream_t stream);
 extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const float* rays, uint32_t* out,
                                               int64_t n, int bvh, hipStream_t stream);
+extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
+                                        hipStream_t stream);
 extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
                                                   uint32_t* first_bad, hipStream_t stream);
 
@@ -1565,6 +1567,81 @@ rtp_status rtp_render_views(rtp_context* c, const rtp_view* views, int32_t n_vie
     stats->kernel_ms = ms;
   }
   return RTP_OK;
+}
+
+// First-hit guides of the path camera (rtp_guides_kernel): one lane per pixel.
+namespace {
+rtp_status launch_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, float* g0, float* g1,
+                         int32_t* prim, hipStream_t stream, double* kernel_ms) {
+  HIP_TRY(hipSetDevice(c->device));
+  rtp::GuideParams p{};
+  camera_setup(cam, nx, ny, &p.cam);
+  p.nx = nx, p.ny = ny, p.npix = (int64_t)nx * ny;
+  p.g0 = g0, p.g1 = g1, p.prim = prim;
+  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
+  HIP_TRY(rtp_launch_guides(c->d_scene, &p, c->use_bvh ? 1 : 0, stream));
+  HIP_TRY(hipEventRecord(c->done, stream));  // (rtp_set_scene waits for it before it frees the scene)
+  c->pending = true;
+  if (kernel_ms) {
+    HIP_TRY(hipEventRecord(c->ev1, stream));
+    HIP_TRY(hipEventSynchronize(c->ev1));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    *kernel_ms = ms;
+  }
+  return RTP_OK;
+}
+rtp_status check_guides_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, bool any_output) {
+  rtp_status rs = check_render_args(c, cam, nx, ny, 0, 1);
+  if (rs != RTP_OK) return rs;
+  if (!any_output) return fail(RTP_ERR_INVALID_ARGUMENT, "render_guides: every output is NULL");
+  return RTP_OK;
+}
+}  // namespace
+
+rtp_status rtp_render_guides_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, float* d_g0,
+                                    float* d_g1, int32_t* d_prim, void* hip_stream, rtp_stats* stats) {
+  rtp_status rs = check_guides_args(c, cam, nx, ny, d_g0 || d_g1 || d_prim);
+  if (rs != RTP_OK) return rs;
+  double ms = 0;
+  rs = launch_guides(c, cam, nx, ny, d_g0, d_g1, d_prim, (hipStream_t)hip_stream, stats ? &ms : nullptr);
+  if (rs == RTP_OK && stats) {
+    *stats = rtp_stats{};
+    stats->samples = (uint64_t)nx * ny;
+    stats->kernel_ms = ms;
+  }
+  return rs;
+}
+
+rtp_status rtp_render_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, float* g0, float* g1,
+                             int32_t* prim, rtp_stats* stats) {
+  rtp_status rs = check_guides_args(c, cam, nx, ny, g0 || g1 || prim);
+  if (rs != RTP_OK) return rs;
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t n = (size_t)nx * ny;
+  void* d[3] = {nullptr, nullptr, nullptr};
+  void* h[3] = {g0, g1, prim};
+  const size_t sz[3] = {16 * n, 16 * n, 4 * n};
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 3 && e == hipSuccess; k++)
+    if (h[k]) e = hipMalloc(&d[k], sz[k]);
+  double ms = 0;
+  if (e == hipSuccess) {
+    rs = launch_guides(c, cam, nx, ny, (float*)d[0], (float*)d[1], (int32_t*)d[2], nullptr, &ms);
+    for (int k = 0; k < 3 && rs == RTP_OK; k++)
+      if (h[k] && (e = hipMemcpy(h[k], d[k], sz[k], hipMemcpyDeviceToHost)) != hipSuccess)
+        rs = hip_fail(e, "render_guides: copy back");
+  } else {
+    rs = hip_fail(e, "render_guides: device buffers");
+  }
+  for (void* p : d)
+    if (p) (void)hipFree(p);
+  if (rs == RTP_OK && stats) {
+    *stats = rtp_stats{};
+    stats->samples = n;
+    stats->kernel_ms = ms;
+  }
+  return rs;
 }
 
 // Diagnostics: sums of the pool kernel's per-wave counters from the last launch

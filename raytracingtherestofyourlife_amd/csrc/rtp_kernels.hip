@@ -519,10 +519,10 @@ RTP_DEV Hit closest_hit(const DevScene* __restrict__ sc, f3 o, f3 d, bool prefil
 }
 
 // Camera::RayGen (Camera.cxx:482-524): 2 draws, jittered direction
+// (camera_ray_at: the same ray for given jitter values ru, rv -- the first-hit
+// guides take the pixel centre, 0.5f twice, and touch no RNG)
 template <class Cam>  // DevCamera, or one read through an address-space-4 (kernarg) reference
-RTP_DEV f3 camera_ray(const Cam& cam, int pi, int pj, int nx, int ny, uint32_t& seed) {
-  float ru = randf(seed);
-  float rv = randf(seed);
+RTP_DEV f3 camera_ray_at(const Cam& cam, int pi, int pj, int nx, int ny, float ru, float rv) {
   f3 rd = add(add(ld3(cam.nlook), scl(ld3(cam.dx), ((2.f * ((float)pi + (1.f - ru)) - (float)nx) / 2.0f))),
               scl(ld3(cam.dy), ((2.f * ((float)pj + rv) - (float)ny) / 2.0f)));
   if (rd.x == 0.f) rd.x += 0.0000001f;
@@ -537,6 +537,12 @@ RTP_DEV f3 camera_ray(const Cam& cam, int pi, int pj, int nx, int ny, uint32_t& 
   // under- or overflows.
   const float r = rcp_nr1(sq_mag);
   return mk(div_markstein(rd.x, sq_mag, r), div_markstein(rd.y, sq_mag, r), div_markstein(rd.z, sq_mag, r));
+}
+template <class Cam>
+RTP_DEV f3 camera_ray(const Cam& cam, int pi, int pj, int nx, int ny, uint32_t& seed) {
+  const float ru = randf(seed);
+  const float rv = randf(seed);
+  return camera_ray_at(cam, pi, pj, nx, ny, ru, rv);
 }
 
 struct Path {
@@ -1631,6 +1637,47 @@ __global__ void __launch_bounds__(256) rtp_eval_closest_kernel(const DevScene* _
   w[6] = full;
 }
 
+// First-hit guides of a path camera (rtp_render_guides_device), one lane per
+// pixel: the ray through the pixel centre (camera_ray_at with 0.5f for both
+// jitter draws), the path kernel's closest_hit, and of that hit the normal
+// shade_hit takes (flipped to face the ray origin), t, the texture colour
+// and the primitive.  No RNG, no render state.
+template <bool kBvh>
+__global__ void __launch_bounds__(256) rtp_guides_kernel(const DevScene* __restrict__ sc, GuideParams p) {
+  __shared__ __align__(16) float s_qshade[kQTableFloats];
+  fill_qshade(sc, s_qshade);
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= p.npix) return;
+  const int pi = (int32_t)i % p.nx, pj = (int32_t)i / p.nx;
+  const f3 o = ld3(p.cam.eye);
+  const f3 d = camera_ray_at(p.cam, pi, pj, p.nx, p.ny, 0.5f, 0.5f);
+  const Hit h = closest_hit<kBvh>(sc, o, d, true, nullptr, s_qshade + kPrexLdsOffset);
+  float4 a = make_float4(0.f, 0.f, 0.f, __builtin_inff()), b = make_float4(0.f, 0.f, 0.f, 0.f);
+  int32_t id = -1;
+  if (h.kind >= 0) {
+    f3 hn, alb;
+    if (h.kind == 0) {
+      const float4* r = reinterpret_cast<const float4*>(s_qshade + h.idx * kQShadeFloats);
+      const float4 r0 = r[0], r1 = r[1];
+      hn = mk(r0.x, r0.y, r0.z);
+      alb = mk(r0.w, r1.x, r1.y);
+    } else {
+      const f3 hp = add(o, scl(d, h.t));
+      const DevSphere& S = kBvh ? sc->sph_all[h.idx] : sc->spheres[h.idx];
+      hn = mk((hp.x - S.c[0]) / S.r, (hp.y - S.c[1]) / S.r, (hp.z - S.c[2]) / S.r);
+      alb = ld3(S.alb);
+    }
+    if (dot(hn, d) > 0.f) hn = neg(hn);
+    a = make_float4(hn.x, hn.y, hn.z, h.t);
+    b = make_float4(alb.x, alb.y, alb.z, 1.f);
+    id = (h.kind << 24) + h.idx;
+  }
+  if (p.g0) reinterpret_cast<float4*>(p.g0)[i] = a;
+  if (p.g1) reinterpret_cast<float4*>(p.g1)[i] = b;
+  if (p.prim) p.prim[i] = id;
+}
+
 // RNG jump tables, all in one pass: thread s iterates the dead-step map from
 // state s (= base + i) up to max_r steps and, after step r, stores the state
 // into every table that tabulates r dead depths (out.t[r] != null: the chain
@@ -1948,5 +1995,16 @@ extern "C" hipError_t rtp_launch_eval_primitive(int kind, const void* in, void* 
   if (grid <= 0) return hipSuccess;
   hipLaunchKernelGGL(rtp::rtp_eval_primitive_kernel, dim3((unsigned)grid), dim3(block), 0, stream, kind, in, out, n,
                      tab, t1, t2);
+  return hipGetLastError();
+}
+
+// (last in the file: its instances are emitted after every other kernel, whose
+// places in the code object stay what they were)
+extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
+                                        hipStream_t stream) {
+  if (p->npix <= 0) return hipSuccess;
+  const dim3 g((unsigned)((p->npix + 255) / 256)), b(256);
+  if (bvh) hipLaunchKernelGGL(rtp::rtp_guides_kernel<true>, g, b, 0, stream, scene, *p);
+  else hipLaunchKernelGGL(rtp::rtp_guides_kernel<false>, g, b, 0, stream, scene, *p);
   return hipGetLastError();
 }

@@ -296,6 +296,28 @@ struct KParams {
   int32_t resume, resume_pad;
 };
 
+// First-hit guides (rtp_guides_kernel): the path camera's constants and the
+// outputs, each nullable, one entry per pixel of the nx x ny canvas.
+struct GuideParams {
+  DevCamera cam;
+  int32_t nx, ny;
+  int64_t npix;   // nx * ny
+  float* g0;      // float4: the unit normal facing the ray origin, t (miss: 0, 0, 0, +inf)
+  float* g1;      // float4: the hit primitive's texture colour, 1 (miss: zeros)
+  int32_t* prim;  // kind << 24 | index (miss: -1)
+};
+
+// One level of the a-trous filter (rtp_atrous_kernel; include/rtp.h
+// rtp_denoise_device has the definition).
+struct AtrousParams {
+  const float* in;   // float4[nx*ny]: rgb, var (var < 0: invalid)
+  const float* g0;   // nullable with g1: normal, t
+  const float* g1;   // albedo, hit flag
+  float* out;        // float4[nx*ny]
+  int32_t nx, ny, step, normal_log2;
+  float sigma_l, sigma_z_step, sigma_a2;  // sigma_z * (float)step and sigma_a * sigma_a, rounded once on the host
+};
+
 // -direct mode (main.cc:120-251): one launch renders the requested AOVs of
 // the quad mappers (MapperQuad colour, MapperQuadNormals, MapperQuadAlbedo)
 // and the canvas depth, one lane per pixel of the canvas.

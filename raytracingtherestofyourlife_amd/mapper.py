@@ -428,6 +428,66 @@ class Device:
                                         ctypes.byref(state), ctypes.byref(st)))
         return st
 
+    # ------------------------------------------------ denoised previews --
+    def render_guides_device(self, camera: Camera, nx: int, ny: int, g0_ptr: int = 0, g1_ptr: int = 0,
+                             prim_ptr: int = 0, stream: int = 0, timed: bool = False):
+        """rtp_render_guides_device: the path camera's first hit per pixel
+        centre into device buffers (each optional): g0_ptr float4[nx*ny]
+        (normal facing the ray, t), g1_ptr float4[nx*ny] (texture colour, hit
+        flag), prim_ptr int32[nx*ny] (kind << 24 | index, -1 on a miss).
+        Asynchronous unless timed."""
+        st = RtpStats()
+        cam = camera.to_c() if camera is not None else None
+        check(self._L.rtp_render_guides_device(self.handle, ctypes.byref(cam) if cam is not None else None, nx, ny,
+                                               ctypes.c_void_p(g0_ptr or None), ctypes.c_void_p(g1_ptr or None),
+                                               ctypes.c_void_p(prim_ptr or None), ctypes.c_void_p(stream or None),
+                                               ctypes.byref(st) if timed else None))
+        return st
+
+    def render_guides(self, camera: Camera, nx: int, ny: int):
+        """rtp_render_guides into host memory: (g0 float32 [nx*ny, 4],
+        g1 float32 [nx*ny, 4], prim int32 [nx*ny], stats)."""
+        n = max(int(nx) * int(ny), 0)
+        g0 = np.zeros((n, 4), dtype=np.float32)
+        g1 = np.zeros((n, 4), dtype=np.float32)
+        prim = np.zeros(n, dtype=np.int32)
+        st = RtpStats()
+        cam = camera.to_c()
+        check(self._L.rtp_render_guides(self.handle, ctypes.byref(cam), nx, ny, g0.ctypes.data_as(_lib.f32p),
+                                        g1.ctypes.data_as(_lib.f32p), prim.ctypes.data_as(_lib.i32p),
+                                        ctypes.byref(st)))
+        return g0, g1, prim, st
+
+    def resolve_device(self, sums_ptr: int, n: int, cv_ptr: int, m2_ptr: int = 0, count_ptr: int = 0, spp: int = 0,
+                       stream: int = 0, timed: bool = False):
+        """rtp_resolve_device: a device-resident render state (sums_ptr
+        float4[n]; m2_ptr float[n] and count_ptr int32[n] optional, without
+        counts every entry has ``spp`` samples) to cv_ptr float4[n]: mean rgb
+        and the variance of the mean luminance (-1: an invalid entry).
+        Asynchronous unless timed."""
+        st = RtpStats()
+        check(self._L.rtp_resolve_device(self.handle, ctypes.c_void_p(sums_ptr or None),
+                                         ctypes.c_void_p(m2_ptr or None), ctypes.c_void_p(count_ptr or None),
+                                         int(spp), int(n), ctypes.c_void_p(cv_ptr or None),
+                                         ctypes.c_void_p(stream or None), ctypes.byref(st) if timed else None))
+        return st
+
+    def denoise_device(self, cv_ptr: int, nx: int, ny: int, out_ptr: int, scratch_ptr: int, g0_ptr: int = 0,
+                       g1_ptr: int = 0, levels: int = 5, sigma_l: float = 4.0, sigma_z: float = 1.0,
+                       sigma_a: float = 0.1, normal_log2: int = 5, stream: int = 0, timed: bool = False):
+        """rtp_denoise_device: ``levels`` levels of the a-trous filter over
+        cv_ptr (float4[nx*ny] from resolve_device) guided by g0_ptr / g1_ptr
+        (both or neither) into out_ptr; scratch_ptr is a second float4[nx*ny].
+        Parameters: include/rtp.h rtp_denoise_params (the defaults are
+        ProgressiveRender.denoised's).  Asynchronous unless timed."""
+        prm = _lib.RtpDenoiseParams(int(levels), float(sigma_l), float(sigma_z), float(sigma_a), int(normal_log2))
+        st = RtpStats()
+        check(self._L.rtp_denoise_device(self.handle, ctypes.c_void_p(cv_ptr or None), ctypes.c_void_p(g0_ptr or None),
+                                         ctypes.c_void_p(g1_ptr or None), nx, ny, ctypes.byref(prm),
+                                         ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(scratch_ptr or None),
+                                         ctypes.c_void_p(stream or None), ctypes.byref(st) if timed else None))
+        return st
+
     FF_POLICIES = {"auto": _lib.RTP_FF_TABLES_AUTO, "off": _lib.RTP_FF_TABLES_OFF, "on": _lib.RTP_FF_TABLES_ON}
 
     def sphere_walk(self) -> str:

@@ -13,12 +13,27 @@ The estimate and the selection rule are pure functions over arrays
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 from .mapper import Camera, Device, ErrorBadValue
 
 LUMA = (0.2126, 0.7152, 0.0722)  # the weights of m2's luminance (include/rtp.h rtp_render_state)
 CHECKPOINT_VERSION = 1
+# ProgressiveRender.denoised's defaults (include/rtp.h rtp_denoise_params; rtp/rendering.hpp has the same)
+DENOISE_LEVELS, DENOISE_SIGMA_L, DENOISE_SIGMA_A, DENOISE_NORMAL_LOG2 = 5, 4.0, 0.1, 5
+
+
+def default_sigma_z(camera: Camera, ny: int) -> float:
+    """The default depth tolerance per pixel of step: the camera's distance to
+    its look-at point spread over the canvas rows, |look_at - position| / ny
+    (computed in double from the float camera, rounded to float32; 1 for a
+    camera that looks at its own position).  It needs no look at the frame."""
+    c = camera.to_c()
+    d = [float(c.look_at[i]) - float(c.position[i]) for i in range(3)]
+    dist = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+    return float(np.float32(dist / ny)) if dist > 0 else 1.0
 
 
 def split_passes(samplecount: int, passes: int) -> list:
@@ -110,6 +125,7 @@ class ProgressiveRender:
         self.live = torch.zeros(n, dtype=torch.int32, device=self._td)
         self.m2 = torch.zeros(n, dtype=torch.float32, device=self._td)
         self.count = torch.zeros(n, dtype=torch.int32, device=self._td)
+        self._guides = None  # guides(): rendered on first use
 
     @property
     def n_pixels(self) -> int:
@@ -168,6 +184,62 @@ class ProgressiveRender:
     def noise(self) -> np.ndarray:
         s = self.state()
         return noise_from_state(s["sums"], s["m2"], s["count"])
+
+    # ----------------------------------------------------------- preview --
+    def guides(self) -> dict:
+        """The camera's first-hit guides (Device.render_guides_device) as
+        device tensors, rendered once and cached: g0 float32 [N, 4] (normal
+        facing the ray, t), g1 float32 [N, 4] (texture colour, hit flag), prim
+        int32 [N].  Asynchronous like step()."""
+        import torch
+
+        if self._guides is None:
+            n = self.n_pixels
+            g0 = torch.empty((n, 4), dtype=torch.float32, device=self._td)
+            g1 = torch.empty((n, 4), dtype=torch.float32, device=self._td)
+            prim = torch.empty(n, dtype=torch.int32, device=self._td)
+            self.device.render_guides_device(self.camera, self.nx, self.ny, g0.data_ptr(), g1.data_ptr(),
+                                             prim.data_ptr(), stream=self._stream())
+            self._guides = dict(g0=g0, g1=g1, prim=prim)
+        return self._guides
+
+    def default_sigma_z(self) -> float:
+        """denoised's default depth tolerance per pixel of step (default_sigma_z above)."""
+        return default_sigma_z(self.camera, self.ny)
+
+    def denoised_device(self, levels: int = DENOISE_LEVELS, sigma_l: float = DENOISE_SIGMA_L, sigma_z=None,
+                        sigma_a: float = DENOISE_SIGMA_A, normal_log2: int = DENOISE_NORMAL_LOG2,
+                        use_guides: bool = True):
+        """The filtered linear means, a device tensor float32 [N, 4] (rgb and
+        the variance of the filtered luminance mean; a pixel nothing could
+        fill keeps (0, 0, 0, -1)): Device.resolve_device on the state, then
+        Device.denoise_device over guides().  Nothing leaves the device and
+        the state is not touched.  Defaults: 5 levels (a 125-pixel-wide
+        footprint), sigma_l 4 standard deviations of the centre's mean,
+        sigma_z default_sigma_z(), sigma_a 0.1 in albedo units, normal_log2 5
+        (cosine to the 32nd power)."""
+        import torch
+
+        n = self.n_pixels
+        g = self.guides() if use_guides else None
+        if sigma_z is None:
+            sigma_z = self.default_sigma_z() if use_guides else 1.0
+        cv = torch.empty((n, 4), dtype=torch.float32, device=self._td)
+        out, scratch = torch.empty_like(cv), torch.empty_like(cv)
+        self.device.resolve_device(self.sums.data_ptr(), n, cv.data_ptr(), m2_ptr=self.m2.data_ptr(),
+                                   count_ptr=self.count.data_ptr(), stream=self._stream())
+        self.device.denoise_device(cv.data_ptr(), self.nx, self.ny, out.data_ptr(), scratch.data_ptr(),
+                                   g0_ptr=g["g0"].data_ptr() if g else 0, g1_ptr=g["g1"].data_ptr() if g else 0,
+                                   levels=levels, sigma_l=sigma_l, sigma_z=sigma_z, sigma_a=sigma_a,
+                                   normal_log2=normal_log2, stream=self._stream())
+        return out
+
+    def denoised(self, **kw) -> np.ndarray:
+        """denoised_device as an image, numpy float32 [N, 4]: sqrt of the rgb
+        like image() (a pixel nothing could fill is black), w = the variance."""
+        a = self.denoised_device(**kw).cpu().numpy()
+        a[:, :3] = np.sqrt(a[:, :3])
+        return a
 
     def refine(self, spp: int, threshold: float, max_spp: int) -> int:
         """One adaptive pass: spp more samples of the pixels select_active

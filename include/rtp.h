@@ -116,6 +116,16 @@ int32_t rtp_abi_version(void);
 rtp_status rtp_create(int32_t device, rtp_context** out);
 void rtp_destroy(rtp_context* ctx);
 
+/* Scenes with 9 or more spheres search them through a BVH whose boxes only
+ * cull.  The closest hit stays the brute-force scan's -- the minimum of (t,
+ * quads before spheres, sphere index) with every sphere tested in float32 --
+ * for every ray whose origin lies within the reach of the sphere it hits: 2
+ * diagonals of the scene's bounding box (every quad vertex, every sphere's
+ * centre -+ radius) from that sphere's centre.  A camera within one diagonal
+ * of the scene, and every scattered ray, is inside it.  From farther away a
+ * ray that passes a sphere's silhouette within the float32 test's own error
+ * (about 5e-3 |o - c|, less the radius) may miss a sphere that the scan would
+ * have reported.  (csrc/rtp_layout.hpp bvh_sphere_pad.) */
 rtp_status rtp_set_scene(rtp_context* ctx, const rtp_scene_desc* scene);
 
 /* Full canvas render into host memory (rgba_out: float4[nx*ny]). */

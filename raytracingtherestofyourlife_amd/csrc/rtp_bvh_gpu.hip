@@ -91,16 +91,17 @@ __global__ void k_karras(const uint32_t* __restrict__ code, int n, int2* __restr
   if (i == 0) parent[0] = -1;
 }
 
-// leaf boxes padded like the host builder; climb while this thread is the
-// second to arrive at the parent
-__global__ void k_boxes(const float4* __restrict__ cr, const uint32_t* __restrict__ idx, int n,
+// leaf boxes padded like the host builder's (rtp_layout.hpp bvh_sphere_pad,
+// `reach` from the scene's bounds); climb while this thread is the second to
+// arrive at the parent
+__global__ void k_boxes(const float4* __restrict__ cr, const uint32_t* __restrict__ idx, int n, float reach,
                         const int2* __restrict__ child, const int* __restrict__ parent, float4* __restrict__ blo,
                         float4* __restrict__ bhi, int* __restrict__ size, int* __restrict__ arrivals) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const int leaf = n - 1 + j;
   const float4 s = cr[idx[j]];
-  const float pad = 0.002f * s.w + 1e-5f + 0x1p-16f * (fmaxf(fabsf(s.x), fmaxf(fabsf(s.y), fabsf(s.z))) + s.w);  // as the host
+  const float pad = bvh_sphere_pad(s.x, s.y, s.z, s.w, reach);
   blo[leaf] = make_float4(s.x - s.w - pad, s.y - s.w - pad, s.z - s.w - pad, 0.f);
   bhi[leaf] = make_float4(s.x + s.w + pad, s.y + s.w + pad, s.z + s.w + pad, 0.f);
   size[leaf] = 1;
@@ -177,9 +178,10 @@ hipError_t dalloc(T** p, size_t count) {
 
 // Builds the 8 octant copies (8 * (2n-1) nodes into d_nodes) and the leaf-
 // order sphere records (n into d_geom) from d_cr (float4 centre + radius per
-// sphere, scene order).  lo / ext: bounding box of the centres.  n >= 2.
-extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, rtp::BvhNode* d_nodes,
-                                        rtp::DevSphereG* d_geom, hipStream_t stream) {
+// sphere, scene order).  lo / ext: bounding box of the centres; reach: the
+// largest |o - c| the boxes are sound for (bvh_sphere_pad).  n >= 2.
+extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, float reach,
+                                        rtp::BvhNode* d_nodes, rtp::DevSphereG* d_geom, hipStream_t stream) {
   using namespace rtp;
   if (n < 2) return hipErrorInvalidValue;
   const int nn = 2 * n - 1;
@@ -226,8 +228,8 @@ extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, fl
   hipLaunchKernelGGL(k_karras, dim3((n - 1 + tb - 1) / tb), dim3(tb), 0, stream, code2, n, child, parent, axis);
   RTP_TRY(hipGetLastError());
   RTP_TRY(hipMemsetAsync(arrivals, 0, sizeof(int) * n, stream));
-  hipLaunchKernelGGL(k_boxes, dim3((n + tb - 1) / tb), dim3(tb), 0, stream, d_cr, idx2, n, child, parent, blo, bhi,
-                     size, arrivals);
+  hipLaunchKernelGGL(k_boxes, dim3((n + tb - 1) / tb), dim3(tb), 0, stream, d_cr, idx2, n, reach, child, parent, blo,
+                     bhi, size, arrivals);
   RTP_TRY(hipGetLastError());
   const int64_t work = (int64_t)nn * 8;
   hipLaunchKernelGGL(k_flatten, dim3((unsigned)((work + tb - 1) / tb)), dim3(tb), 0, stream, d_cr, idx2, n, child,

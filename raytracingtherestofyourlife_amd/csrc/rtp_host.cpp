@@ -33,8 +33,8 @@ extern "C" hipError_t rtp_launch_build_ff_tables(const rtp::FfBuildOut* out, int
                                                  hipStream_t stream);
 extern "C" hipError_t rtp_compact_bvh(const rtp::BvhNode* d_nodes, int64_t total, uint32_t* d_cn, int32_t* d_cidx,
                                       hipStream_t stream);
-extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, rtp::BvhNode* d_nodes,
-                                        rtp::DevSphereG* d_geom, hipStream_t stream);
+extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, float reach,
+                                        rtp::BvhNode* d_nodes, rtp::DevSphereG* d_geom, hipStream_t stream);
 extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const float* rays, uint32_t* out,
                                               int64_t n, int bvh, hipStream_t stream);
 extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
@@ -403,9 +403,10 @@ FfSnap ff_tables(int device, int policy, uint64_t samples) {
 // depth-first "threaded" array (hit: next node; miss or leaf done: skip) that
 // visits the child on the near side of the split axis first, so a lane walks
 // near-to-far without a stack and the closest-hit bound culls early.  Boxes
-// only cull: each sphere box is padded by 0.2% of its radius + 1e-5 so that
-// every point the device's float sphere test can return lies inside it, and
-// the kernel compares against a slack-widened [0, t_best] interval.  The
+// only cull: each sphere box is padded (rtp_layout.hpp bvh_sphere_pad, from
+// the roundings of the device's float sphere test) so that every ray that
+// test accepts, and the point it returns, lie inside it, and the kernel
+// compares against a slack-widened [0, t_best] interval.  The
 // closest hit is the lexicographic min of (t, kind, index) whatever the order.
 struct BvhPrim {
   float lo[3], hi[3], cen[3];
@@ -766,6 +767,23 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     st(S.alb, ld(s->tex_rgb + 3 * s->tex_type[s->sphere_tex[k]]));
   }
   const bool use_bvh = s->n_spheres >= rtp::kBvhMinSpheres;
+  // The reach of the sphere boxes' pad (rtp_layout.hpp bvh_sphere_pad):
+  // kBvhReachFactor diagonals of the scene's bounding box -- every quad
+  // vertex, every sphere's c -+ r.
+  float bvh_reach = 0.f;
+  if (use_bvh) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int q = 0; q < s->n_quads; q++)
+      for (int c2 = 0; c2 < 4; c2++)
+        for (int k = 0; k < 3; k++) {
+          const float v = s->points[3 * s->quad_points[4 * q + c2] + k];
+          lo[k] = std::min(lo[k], v), hi[k] = std::max(hi[k], v);
+        }
+    for (const rtp::DevSphere& S : sph)
+      for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], S.c[k] - S.r), hi[k] = std::max(hi[k], S.c[k] + S.r);
+    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+    bvh_reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
+  }
   // which builder makes the sphere BVH: the host's binned SAH (better trees,
   // O(n log n) on one core) or the device LBVH (rtp_bvh_gpu.hip) for large
   // scenes; RTP_BVH_BUILD=host|gpu overrides
@@ -788,10 +806,9 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     std::vector<BvhPrim> P(s->n_spheres);
     for (int k = 0; k < s->n_spheres; k++) {
       const rtp::DevSphere& S = sph[k];
-      // (+ 2^-16 of the coordinates' magnitude: the walk's fma slab test,
-      // rtp_kernels.hip BvhRay, stays far inside the margin at any scale)
-      const float pad = 0.002f * S.r + 1e-5f +
-                        0x1p-16f * (std::max(std::fabs(S.c[0]), std::max(std::fabs(S.c[1]), std::fabs(S.c[2]))) + S.r);
+      // (the slab test's margin and what float32 sphere_root accepts beyond
+      // the sphere: derived in rtp_layout.hpp; the same call in k_boxes)
+      const float pad = rtp::bvh_sphere_pad(S.c[0], S.c[1], S.c[2], S.r, bvh_reach);
       for (int a = 0; a < 3; a++) {
         P[k].lo[a] = S.c[a] - S.r - pad;
         P[k].hi[a] = S.c[a] + S.r + pad;
@@ -922,8 +939,8 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     if (e == hipSuccess) e = hipMemcpy(d_cr, cr.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice);
     if (e == hipSuccess)
       e = rtp_build_bvh_gpu(d_cr, n, make_float3(lo[0], lo[1], lo[2]),
-                            make_float3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]), c->d_nodes, c->d_sph_geom,
-                            nullptr);
+                            make_float3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]), bvh_reach, c->d_nodes,
+                            c->d_sph_geom, nullptr);
     if (d_cr) (void)hipFree(d_cr);
     if (e == hipSuccess)
       e = hipMemcpy(c->d_sph_all, sph.data(), sph.size() * sizeof(rtp::DevSphere), hipMemcpyHostToDevice);

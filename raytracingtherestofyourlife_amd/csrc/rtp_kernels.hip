@@ -159,10 +159,12 @@ RTP_DEV float slab_rcp(float v) { return __builtin_amdgcn_rcpf(fabsf(v) < 1e-20f
 // the generic ones loaded from the scene the walk compiled to flat loads.)
 // The slab test runs as fma(box, 1/d, -o/d): one rounding of o/d per
 // component instead of a rounded (box - o) per face.  The boxes only cull,
-// and each sphere lies at least the host's pad inside its boxes on every
-// axis (rtp_host.cpp: 0.002 r + 1e-5 + 2^-16 (|c| + r)), so a ray through
-// a sphere crosses every box around it over a parameter interval 2 pad / |d|
-// wider than the sphere's: far above these roundings (2^-24 |o| / |d|).
+// and each sphere lies at least the builders' pad inside its boxes on every
+// axis (rtp_layout.hpp bvh_sphere_pad).  Its first part, 0.002 r + 1e-5 +
+// 2^-16 (|c| + r), is this test's: a ray through a sphere crosses every box
+// around it over a parameter interval 2 pad / |d| wider than the sphere's,
+// far above these roundings (2^-24 |o| / |d|).  Its second part covers what
+// sphere_root accepts beyond the exact sphere (its discriminant's roundings).
 struct BvhRay {
   GU4* nodes;
   GI32* cidx;

@@ -104,6 +104,50 @@ struct alignas(16) BvhNode {
   float hi[3];
   int32_t leaf;  // 0: inner; kBvhLeafSphere: one embedded sphere; else (first << 3) | count
 };
+// The pad of a sphere's box (both builders: rtp_host.cpp rtp_set_scene,
+// rtp_bvh_gpu.hip k_boxes).  The boxes only cull, which is sound only if
+// every ray that the float32 sphere_root (rtp_kernels.hip) accepts for a
+// sphere crosses every box around it, and the point at the accepted t lies in
+// them (then the box's entry parameter is <= t, and the walk's "entry <= best
+// t" cull cannot drop a sphere whose root would win).  sphere_root's own
+// roundings decide what it accepts.  With u = 2^-24, D = |o - c|, a = |d|^2,
+// M = max(D, r), to first order in u:
+//   oc = o - c            each component within u: |oc' - oc| <= u D
+//   b  = dot(oc, d)       3 products, 2 sums: |b' - b| <= (1 + 3) u D |d|
+//   b b                   |.| <= 2 |b| 4 u D |d| + u b^2     <=  9 u a D^2
+//   cc = dot(oc, oc) - rr (2 + 3) u D^2 + u r^2 + u |cc|     <=  8 u M^2
+//   a  = dot(d, d)        3 u a
+//   a cc                  a 8 u M^2 + (3 + 1) u a |cc|       <= 12 u a M^2
+//   disc = b b - a cc     the difference's rounding           <=  2 u a M^2
+// so |disc' - disc| <= 23 u a M^2 (24 with the second-order terms), and
+// disc = a (r^2 - p^2) for a ray passing the centre at distance p: float32
+// accepts only rays with p^2 < r^2 + E, E = 24 u M^2, whatever |d|.  The
+// point at T = (-b -+ sqrt(disc')) / a lies at distance sqrt(r^2 + (disc' -
+// disc) / a) <= sqrt(r^2 + E) from c; the roundings of b, the root and the
+// quotient move the accepted t by less than 10 u M / |d| from T, and the
+// slab test's one rounding of o / d (rtp_kernels.hip BvhRay) by 2 u |o| / |d|.
+// Hence the pad: (sqrt(r^2 + E) - r) + 16 u reach on top of the slab test's
+// 0.002 r + 1e-5 + 2^-16 (max|c| + r), for every origin within `reach` of the
+// sphere's centre (M <= reach: the reach exceeds every radius).  The reach is
+// kBvhReachFactor diagonals of the scene's bounding box (every quad vertex,
+// every sphere's c -+ r; include/rtp.h rtp_set_scene): from a camera within
+// one diagonal of the scene every sphere is within two.  The margin grows
+// with reach / r: small next to the radius for spheres above ~1% of the
+// scene, several radii for spheres of 1e-3 of it -- which is how far off
+// float32 accepts them (tests/test_sphere_zoo.py counts it).
+constexpr float kBvhReachFactor = 2.0f;
+constexpr float kBvhDiscErr = 0x1.8p-20f;     // 24 * 2^-24
+constexpr float kBvhReachRound = 0x1p-20f;    // 16 * 2^-24
+#ifdef __HIP__
+__attribute__((host)) __attribute__((device))
+#endif
+inline float bvh_sphere_pad(float cx, float cy, float cz, float r, float reach) {
+  const float amax = __builtin_fmaxf(__builtin_fabsf(cx), __builtin_fmaxf(__builtin_fabsf(cy), __builtin_fabsf(cz)));
+  const float slab = 0.002f * r + 1e-5f + 0x1p-16f * (amax + r);
+  const float E = kBvhDiscErr * reach * reach;
+  return slab + (__builtin_sqrtf(r * r + E) - r) + kBvhReachRound * reach;
+}
+
 // leaf value of a one-sphere leaf that holds the sphere itself: lo = centre,
 // hi[0] = radius^2, hi[1] = sphere index (int bits)
 constexpr int32_t kBvhLeafSphere = -1;

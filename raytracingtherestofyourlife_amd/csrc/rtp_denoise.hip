@@ -125,17 +125,12 @@ __global__ void __launch_bounds__(kAtrousBX* kAtrousBY) rtp_atrous_kernel(Atrous
 
 }  // namespace rtp
 
-namespace {
+// ------------------------------------------------------------ host half ---
+#include "rtp_host_util.hpp"
 
-rtp_status hip_fail(hipError_t e, const char* what) {
-  return rtp_internal_fail(e == hipErrorOutOfMemory ? RTP_ERR_OUT_OF_MEMORY : RTP_ERR_DEVICE,
-                           std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
+using namespace rtp_host;
+
+namespace {
 
 rtp_status bad(const char* msg) { return rtp_internal_fail(RTP_ERR_INVALID_ARGUMENT, msg); }
 
@@ -169,49 +164,38 @@ rtp_status launch_denoise(rtp_context* c, const float* cv, const float* g0, cons
                           const rtp_denoise_params* q, float* out, float* scratch, hipStream_t stream,
                           double* kernel_ms) {
   HIP_TRY(hipSetDevice(c->device));
-  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
   const dim3 grid((unsigned)((nx + rtp::kAtrousBX - 1) / rtp::kAtrousBX),
                   (unsigned)((ny + rtp::kAtrousBY - 1) / rtp::kAtrousBY)),
       block(rtp::kAtrousBX * rtp::kAtrousBY);
-  const float* src = cv;
-  for (int s = 0; s < q->levels; s++) {
-    rtp::AtrousParams p{};
-    p.in = src, p.g0 = g0, p.g1 = g1;
-    p.out = ((q->levels - 1 - s) % 2 == 0) ? out : scratch;
-    p.nx = nx, p.ny = ny, p.step = 1 << s, p.normal_log2 = q->normal_log2;
-    p.sigma_l = q->sigma_l;
-    p.sigma_z_step = q->sigma_z * (float)p.step;
-    p.sigma_a2 = q->sigma_a * q->sigma_a;
-    if (g0) hipLaunchKernelGGL(rtp::rtp_atrous_kernel<true>, grid, block, 0, stream, p);
-    else hipLaunchKernelGGL(rtp::rtp_atrous_kernel<false>, grid, block, 0, stream, p);
-    HIP_TRY(hipGetLastError());
-    src = p.out;
-  }
-  if (kernel_ms) {
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *kernel_ms = ms;
-  }
-  return RTP_OK;
+  // (these kernels read no per-context state: rtp_context::done is not recorded)
+  return timed_launch(c, stream, kernel_ms, false, [&]() -> rtp_status {
+    const float* src = cv;
+    for (int s = 0; s < q->levels; s++) {
+      rtp::AtrousParams p{};
+      p.in = src, p.g0 = g0, p.g1 = g1;
+      p.out = ((q->levels - 1 - s) % 2 == 0) ? out : scratch;
+      p.nx = nx, p.ny = ny, p.step = 1 << s, p.normal_log2 = q->normal_log2;
+      p.sigma_l = q->sigma_l;
+      p.sigma_z_step = q->sigma_z * (float)p.step;
+      p.sigma_a2 = q->sigma_a * q->sigma_a;
+      if (g0) hipLaunchKernelGGL(rtp::rtp_atrous_kernel<true>, grid, block, 0, stream, p);
+      else hipLaunchKernelGGL(rtp::rtp_atrous_kernel<false>, grid, block, 0, stream, p);
+      HIP_TRY(hipGetLastError());
+      src = p.out;
+    }
+    return RTP_OK;
+  });
 }
 
 rtp_status launch_resolve(rtp_context* c, const float* sums, const float* m2, const int32_t* count, int32_t spp,
                           int64_t n, float* cv, hipStream_t stream, double* kernel_ms) {
   HIP_TRY(hipSetDevice(c->device));
-  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
-  hipLaunchKernelGGL(rtp::rtp_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                     reinterpret_cast<const float4*>(sums), m2, count, spp, n, reinterpret_cast<float4*>(cv));
-  HIP_TRY(hipGetLastError());
-  if (kernel_ms) {
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *kernel_ms = ms;
-  }
-  return RTP_OK;
+  return timed_launch(c, stream, kernel_ms, false, [&]() -> rtp_status {
+    hipLaunchKernelGGL(rtp::rtp_resolve_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       reinterpret_cast<const float4*>(sums), m2, count, spp, n, reinterpret_cast<float4*>(cv));
+    HIP_TRY(hipGetLastError());
+    return RTP_OK;
+  });
 }
 
 rtp_status check_resolve(rtp_context* c, const float* sums, int64_t n, const float* cv) {
@@ -220,59 +204,33 @@ rtp_status check_resolve(rtp_context* c, const float* sums, int64_t n, const flo
   return RTP_OK;
 }
 
-void fill_stats(rtp_stats* stats, uint64_t n, double ms) {
-  if (!stats) return;
-  *stats = rtp_stats{};
-  stats->samples = n;
-  stats->kernel_ms = ms;
-}
-
-// device copies of host buffers for the synchronous variants
-struct DevBufs {
-  void* p[8] = {};
-  int n = 0;
-  ~DevBufs() {
-    for (int i = 0; i < n; i++)
-      if (p[i]) (void)hipFree(p[i]);
-  }
-  // a device buffer of `bytes`, filled from host when host != NULL
-  hipError_t get(const void* host, size_t bytes, void** out) {
-    hipError_t e = hipMalloc(&p[n], bytes);
-    if (e != hipSuccess) return e;
-    *out = p[n++];
-    return host ? hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice) : hipSuccess;
-  }
-};
-
 }  // namespace
 
 extern "C" {
 
 rtp_status rtp_resolve_device(rtp_context* c, const float* d_sums, const float* d_m2, const int32_t* d_count,
                               int32_t spp, int64_t n, float* d_cv, void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_resolve(c, d_sums, n, d_cv);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_resolve(c, d_sums, n, d_cv));
   double ms = 0;
-  rs = launch_resolve(c, d_sums, d_m2, d_count, spp, n, d_cv, (hipStream_t)hip_stream, stats ? &ms : nullptr);
-  if (rs == RTP_OK) fill_stats(stats, (uint64_t)n, ms);
-  return rs;
+  RTP_TRY(launch_resolve(c, d_sums, d_m2, d_count, spp, n, d_cv, (hipStream_t)hip_stream, stats ? &ms : nullptr));
+  fill_stats(stats, (uint64_t)n, ms);
+  return RTP_OK;
 }
 
 rtp_status rtp_resolve(rtp_context* c, const float* sums, const float* m2, const int32_t* count, int32_t spp,
                        int64_t n, float* cv, rtp_stats* stats) {
-  rtp_status rs = check_resolve(c, sums, n, cv);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_resolve(c, sums, n, cv));
   HIP_TRY(hipSetDevice(c->device));
   DevBufs b;
-  void *ds = nullptr, *dm = nullptr, *dc = nullptr, *dv = nullptr;
-  HIP_TRY(b.get(sums, (size_t)n * 16, &ds));
-  if (m2) HIP_TRY(b.get(m2, (size_t)n * 4, &dm));
-  if (count) HIP_TRY(b.get(count, (size_t)n * 4, &dc));
-  HIP_TRY(b.get(nullptr, (size_t)n * 16, &dv));
+  float *ds = nullptr, *dm = nullptr, *dv = nullptr;
+  int32_t* dc = nullptr;
+  HIP_TRY(b.get(&ds, (size_t)n * 16, sums));
+  if (m2) HIP_TRY(b.get(&dm, (size_t)n * 4, m2));
+  if (count) HIP_TRY(b.get(&dc, (size_t)n * 4, count));
+  HIP_TRY(b.get(&dv, (size_t)n * 16));
   double ms = 0;
-  rs = launch_resolve(c, (const float*)ds, (const float*)dm, (const int32_t*)dc, spp, n, (float*)dv, nullptr, &ms);
-  if (rs != RTP_OK) return rs;
-  HIP_TRY(hipMemcpy(cv, dv, (size_t)n * 16, hipMemcpyDeviceToHost));
+  RTP_TRY(launch_resolve(c, ds, dm, dc, spp, n, dv, nullptr, &ms));
+  HIP_TRY(DevBufs::back(cv, dv, (size_t)n * 16));
   fill_stats(stats, (uint64_t)n, ms);
   return RTP_OK;
 }
@@ -280,35 +238,31 @@ rtp_status rtp_resolve(rtp_context* c, const float* sums, const float* m2, const
 rtp_status rtp_denoise_device(rtp_context* c, const float* d_cv, const float* d_g0, const float* d_g1, int32_t nx,
                               int32_t ny, const rtp_denoise_params* params, float* d_out, float* d_scratch,
                               void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_denoise(c, d_cv, d_g0, d_g1, nx, ny, params, d_out, d_scratch, true);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_denoise(c, d_cv, d_g0, d_g1, nx, ny, params, d_out, d_scratch, true));
   double ms = 0;
-  rs = launch_denoise(c, d_cv, d_g0, d_g1, nx, ny, params, d_out, d_scratch, (hipStream_t)hip_stream,
-                      stats ? &ms : nullptr);
-  if (rs == RTP_OK) fill_stats(stats, (uint64_t)nx * (uint64_t)ny, ms);
-  return rs;
+  RTP_TRY(launch_denoise(c, d_cv, d_g0, d_g1, nx, ny, params, d_out, d_scratch, (hipStream_t)hip_stream,
+                         stats ? &ms : nullptr));
+  fill_stats(stats, (uint64_t)nx * (uint64_t)ny, ms);
+  return RTP_OK;
 }
 
 rtp_status rtp_denoise(rtp_context* c, const float* cv, const float* g0, const float* g1, int32_t nx, int32_t ny,
                        const rtp_denoise_params* params, float* out, rtp_stats* stats) {
-  rtp_status rs = check_denoise(c, cv, g0, g1, nx, ny, params, out, nullptr, false);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_denoise(c, cv, g0, g1, nx, ny, params, out, nullptr, false));
   HIP_TRY(hipSetDevice(c->device));
   const size_t bytes = (size_t)nx * (size_t)ny * 16;
   DevBufs b;
-  void *dv = nullptr, *d0 = nullptr, *d1 = nullptr, *dout = nullptr, *dscr = nullptr;
-  HIP_TRY(b.get(cv, bytes, &dv));
+  float *dv = nullptr, *d0 = nullptr, *d1 = nullptr, *dout = nullptr, *dscr = nullptr;
+  HIP_TRY(b.get(&dv, bytes, cv));
   if (g0) {
-    HIP_TRY(b.get(g0, bytes, &d0));
-    HIP_TRY(b.get(g1, bytes, &d1));
+    HIP_TRY(b.get(&d0, bytes, g0));
+    HIP_TRY(b.get(&d1, bytes, g1));
   }
-  HIP_TRY(b.get(nullptr, bytes, &dout));
-  HIP_TRY(b.get(nullptr, bytes, &dscr));
+  HIP_TRY(b.get(&dout, bytes));
+  HIP_TRY(b.get(&dscr, bytes));
   double ms = 0;
-  rs = launch_denoise(c, (const float*)dv, (const float*)d0, (const float*)d1, nx, ny, params, (float*)dout,
-                      (float*)dscr, nullptr, &ms);
-  if (rs != RTP_OK) return rs;
-  HIP_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+  RTP_TRY(launch_denoise(c, dv, d0, d1, nx, ny, params, dout, dscr, nullptr, &ms));
+  HIP_TRY(DevBufs::back(out, dout, bytes));
   fill_stats(stats, (uint64_t)nx * (uint64_t)ny, ms);
   return RTP_OK;
 }

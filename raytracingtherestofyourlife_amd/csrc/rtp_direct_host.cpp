@@ -22,38 +22,18 @@
 
 #include "../../include/rtp.h"
 #include "rtp_context.hpp"
+#include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
 
 extern "C" hipError_t rtp_launch_direct(const rtp::DevScene* scene, const rtp::DirectParams* p, hipStream_t stream);
 extern "C" hipError_t rtp_launch_eval_powf(const float* x, float y, float* out, int64_t n, hipStream_t stream);
 
+using namespace rtp_host;
+
 namespace {
 
-rtp_status fail(rtp_status st, const std::string& msg) { return rtp_internal_fail(st, msg); }
-rtp_status hip_fail(hipError_t e, const char* what) {
-  return fail(e == hipErrorOutOfMemory ? RTP_ERR_OUT_OF_MEMORY : RTP_ERR_DEVICE,
-              std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-struct v3 {
-  float x, y, z;
-};
-inline v3 add(v3 a, v3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-inline v3 sub(v3 a, v3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline v3 scl(v3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline v3 cross(v3 a, v3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline v3 normalize(v3 a) { return scl(a, 1 / std::sqrt(dot(a, a))); }  // vtkm::Normalize (CPU build)
-inline v3 ld(const float* p) { return {p[0], p[1], p[2]}; }
-inline void st(float* d, v3 a) { d[0] = a.x, d[1] = a.y, d[2] = a.z; }
 inline float std_max(float a, float b) { return (a < b) ? b : a; }  // vtkm::Max on the CPU build
 inline float std_min(float a, float b) { return (b < a) ? b : a; }  // vtkm::Min
-constexpr float kPi180f = 0.01745329251994329577f;                  // vtkm::Pi_180f()
 
 struct M4 {
   float m[4][4];
@@ -213,11 +193,7 @@ void direct_setup(const rtp_context* c, const rtp_camera* cam, const rtp_direct_
 rtp_status check_direct(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, const rtp_direct_desc* dd,
                         bool any_out) {
   if (!c || !cam || !dd) return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: NULL argument");
-  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "render_direct: rtp_set_scene was not called");
-  if (nx <= 0 || ny <= 0) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera width/height must be greater than zero.");
-  if ((int64_t)nx * ny > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: canvas too large");
-  if (!(cam->fov_y_deg > 0)) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera feild of view must be greater than zero.");
-  if (cam->fov_y_deg > 180) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera feild of view must be less than 180.");
+  RTP_TRY(check_canvas_camera(c, cam, nx, ny, "render_direct"));
   if (!any_out) return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: no output buffer");
   if (c->n_ref_quads > 0 && !dd->quad_scalar)
     return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: quad_scalar is NULL");
@@ -238,10 +214,7 @@ rtp_status stage_inputs(rtp_context* c, const rtp_direct_desc* dd, bool need_cma
   host.resize(cm_off + 4 * (size_t)cm + 1);
   if (cm) std::memcpy(host.data() + cm_off, dd->color_map, sizeof(float) * 4 * cm);
   const size_t bytes = host.size() * sizeof(float);
-  if (c->pending) {
-    HIP_TRY(hipEventSynchronize(c->done));
-    c->pending = false;
-  }
+  RTP_TRY(drain(c));
   if (bytes > c->direct_bytes) {
     if (c->d_direct) HIP_TRY(hipFree(c->d_direct));
     c->d_direct = nullptr;
@@ -262,21 +235,12 @@ rtp_status launch_direct(rtp_context* c, const rtp_camera* cam, int32_t nx, int3
   HIP_TRY(hipSetDevice(c->device));
   rtp::DirectParams p{};
   direct_setup(c, cam, dd, nx, ny, &p);
-  rtp_status rs = stage_inputs(c, dd, color != nullptr, stream, &p);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(stage_inputs(c, dd, color != nullptr, stream, &p));
   p.color = color, p.normals = normals, p.albedo = albedo, p.depth = depth;
-  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
-  HIP_TRY(rtp_launch_direct(c->d_scene, &p, stream));
-  HIP_TRY(hipEventRecord(c->done, stream));
-  c->pending = true;
-  if (kernel_ms) {
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *kernel_ms = ms;
-  }
-  return RTP_OK;
+  return timed_launch(c, stream, kernel_ms, true, [&]() -> rtp_status {
+    HIP_TRY(rtp_launch_direct(c->d_scene, &p, stream));
+    return RTP_OK;
+  });
 }
 
 // ColorTable node (x, value) kept sorted by x (ColorTable::AddPoint)
@@ -329,49 +293,31 @@ extern "C" {
 rtp_status rtp_render_direct(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny,
                              const rtp_direct_desc* dd, float* color, float* normals, float* albedo, float* depth,
                              rtp_stats* stats) {
-  rtp_status rs = check_direct(c, cam, nx, ny, dd, color || normals || albedo || depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_direct(c, cam, nx, ny, dd, color || normals || albedo || depth));
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)nx * ny;
+  DevBufs b;
   float* d[4] = {nullptr, nullptr, nullptr, nullptr};
   float* h[4] = {color, normals, albedo, depth};
   const size_t sz[4] = {16 * n, 16 * n, 16 * n, 4 * n};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 4 && e == hipSuccess; k++)
-    if (h[k]) e = hipMalloc(&d[k], sz[k]);
+  for (int k = 0; k < 4; k++)
+    if (h[k]) HIP_TRY_AS("render_direct: device buffers", b.get(&d[k], sz[k]));
   double ms = 0;
-  if (e == hipSuccess) {
-    rs = launch_direct(c, cam, nx, ny, dd, d[0], d[1], d[2], d[3], nullptr, &ms);
-    for (int k = 0; k < 4 && rs == RTP_OK; k++)
-      if (h[k] && (e = hipMemcpy(h[k], d[k], sz[k], hipMemcpyDeviceToHost)) != hipSuccess)
-        rs = hip_fail(e, "render_direct: copy back");
-  } else {
-    rs = hip_fail(e, "render_direct: device buffers");
-  }
-  for (float* p : d)
-    if (p) (void)hipFree(p);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = n;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RTP_TRY(launch_direct(c, cam, nx, ny, dd, d[0], d[1], d[2], d[3], nullptr, &ms));
+  for (int k = 0; k < 4; k++) HIP_TRY_AS("render_direct: copy back", DevBufs::back(h[k], d[k], sz[k]));
+  fill_stats(stats, n, ms);
+  return RTP_OK;
 }
 
 rtp_status rtp_render_direct_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny,
                                     const rtp_direct_desc* dd, float* color, float* normals, float* albedo,
                                     float* depth, void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_direct(c, cam, nx, ny, dd, color || normals || albedo || depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_direct(c, cam, nx, ny, dd, color || normals || albedo || depth));
   double ms = 0;
-  rs = launch_direct(c, cam, nx, ny, dd, color, normals, albedo, depth, (hipStream_t)hip_stream,
-                     stats ? &ms : nullptr);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = (uint64_t)nx * ny;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RTP_TRY(launch_direct(c, cam, nx, ny, dd, color, normals, albedo, depth, (hipStream_t)hip_stream,
+                        stats ? &ms : nullptr));
+  fill_stats(stats, (uint64_t)nx * ny, ms);
+  return RTP_OK;
 }
 
 // ColorTable(name, colorSpace, nanColor, rgbPoints, alphaPoints) ->
@@ -474,15 +420,12 @@ rtp_status rtp_eval_powf(rtp_context* c, const float* x, float y, float* out, in
   if (!c || !x || !out || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_eval_powf: bad arguments");
   if (n == 0) return RTP_OK;
   HIP_TRY(hipSetDevice(c->device));
+  DevBufs b;
   float *dx = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&dx, (size_t)n * 4));
-  hipError_t e = hipMalloc(&dout, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMemcpy(dx, x, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = rtp_launch_eval_powf(dx, y, dout, n, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(dx);
-  if (dout) (void)hipFree(dout);
-  if (e != hipSuccess) return hip_fail(e, "rtp_eval_powf");
+  HIP_TRY_AS("rtp_eval_powf", b.get(&dx, (size_t)n * 4, x));
+  HIP_TRY_AS("rtp_eval_powf", b.get(&dout, (size_t)n * 4));
+  HIP_TRY_AS("rtp_eval_powf", rtp_launch_eval_powf(dx, y, dout, n, nullptr));
+  HIP_TRY_AS("rtp_eval_powf", DevBufs::back(out, dout, (size_t)n * 4));
   return RTP_OK;
 }
 

@@ -14,12 +14,14 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rtp.h"
 #include "rtp_context.hpp"
+#include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
 
 extern "C" int64_t rtp_plan_history_lanes(int64_t npix, int spp, int bvh, int* variant_out, int* waves_out);
@@ -42,36 +44,11 @@ extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::G
 extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
                                                   uint32_t* first_bad, hipStream_t stream);
 
+using namespace rtp_host;
+
 namespace {
 
 thread_local std::string g_err;
-
-rtp_status fail(rtp_status st, const std::string& msg) {
-  g_err = msg;
-  return st;
-}
-rtp_status hip_fail(hipError_t e, const char* what) {
-  return fail(e == hipErrorOutOfMemory ? RTP_ERR_OUT_OF_MEMORY : RTP_ERR_DEVICE,
-              std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIP_TRY(expr)                                 \
-  do {                                                \
-    hipError_t e_ = (expr);                           \
-    if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-  } while (0)
-
-// ---------------------------------------------------- host vector math ---
-struct v3 {
-  float x, y, z;
-};
-inline v3 sub(v3 a, v3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-inline v3 scl(v3 a, float s) { return {a.x * s, a.y * s, a.z * s}; }
-inline float dot(v3 a, v3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-inline v3 cross(v3 a, v3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-inline float rmag(v3 a) { return 1 / std::sqrt(dot(a, a)); }
-inline v3 normalize(v3 a) { return scl(a, rmag(a)); }  // vtkm::Normalize (CPU build)
-inline v3 ld(const float* p) { return {p[0], p[1], p[2]}; }
-inline void st(float* d, v3 a) { d[0] = a.x, d[1] = a.y, d[2] = a.z; }
 
 // which = min(3, int(r*3+1)), r = float(t)/4294967295.f  (PdfWorklet.h:20)
 int which_of_hash(uint32_t t) {
@@ -141,8 +118,7 @@ void setup_prefilter(rtp::DevScene* h, const rtp_scene_desc* s, const std::vecto
   h->pre_scale = 0.0f;
   const int n = h->kind_begin[6];
   if (n <= 0 || n > rtp::kMaxPre) return;
-  const char* e = getenv("RTP_PREFILTER");
-  if (e && e[0] == '0') return;
+  if (env_is("RTP_PREFILTER", '0')) return;
   std::vector<int> axis_of(n);
   std::vector<rtp::PreQuad> pq(n);
   float scale = 0.0f;
@@ -565,14 +541,19 @@ void bvh_flatten(const std::vector<TNode>& T, int t, int oct, const std::vector<
 }  // namespace
 
 // error reporting for the other translation units of librtp.so
-rtp_status rtp_internal_fail(rtp_status st, const std::string& msg) { return fail(st, msg); }
+rtp_status rtp_internal_fail(rtp_status st, const std::string& msg) {
+  g_err = msg;
+  return st;
+}
 
 namespace {
-rtp_status drain(rtp_context* c) {
-  if (c->pending) {
-    HIP_TRY(hipEventSynchronize(c->done));
-    c->pending = false;
-  }
+// the device buffers and events every context owns from rtp_create on
+rtp_status create_resources(rtp_context* c) {
+  HIP_TRY_AS("hipMalloc(scene)", hipMalloc(&c->d_scene, sizeof(rtp::DevScene)));
+  HIP_TRY_AS("hipMalloc(progress)", hipMalloc(&c->d_progress, 16));
+  HIP_TRY(hipEventCreate(&c->ev0));
+  HIP_TRY(hipEventCreate(&c->ev1));
+  HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
   return RTP_OK;
 }
 }  // namespace
@@ -593,43 +574,22 @@ rtp_status rtp_create(int32_t device, rtp_context** out) {
   rtp_context* c = new rtp_context();
   c->device = device;
   c->ff_policy = ff_policy_default();
-  e = hipMalloc(&c->d_scene, sizeof(rtp::DevScene));
-  if (e != hipSuccess) {
-    delete c;
-    return hip_fail(e, "hipMalloc(scene)");
-  }
-  e = hipMalloc(&c->d_progress, 16);
-  if (e != hipSuccess) {
-    (void)hipFree(c->d_scene);
-    delete c;
-    return hip_fail(e, "hipMalloc(progress)");
-  }
-  HIP_TRY(hipEventCreate(&c->ev0));
-  HIP_TRY(hipEventCreate(&c->ev1));
-  HIP_TRY(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
-  *out = c;
-  return RTP_OK;
+  const rtp_status rs = create_resources(c);
+  if (rs != RTP_OK) rtp_destroy(c);  // (the one clean-up path: releases what was made, keeps the message)
+  else *out = c;
+  return rs;
 }
 
 void rtp_destroy(rtp_context* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)drain(c);
-  if (c->d_scene) (void)hipFree(c->d_scene);
-  if (c->d_hist) (void)hipFree(c->d_hist);
-  if (c->d_dbg) (void)hipFree(c->d_dbg);
-  if (c->d_progress) (void)hipFree(c->d_progress);
-  if (c->d_nodes) (void)hipFree(c->d_nodes);
-  if (c->d_sph_geom) (void)hipFree(c->d_sph_geom);
-  if (c->d_sph_all) (void)hipFree(c->d_sph_all);
-  for (void* p : {(void*)c->d_lw_nodes, (void*)c->d_lw_cidx, (void*)c->d_lw_sph, (void*)c->d_lw_orig})
+  for (void* p : {(void*)c->d_scene, (void*)c->d_hist, (void*)c->d_dbg, (void*)c->d_progress, (void*)c->d_nodes,
+                  (void*)c->d_sph_geom, (void*)c->d_sph_all, (void*)c->d_lw_nodes, (void*)c->d_lw_cidx,
+                  (void*)c->d_lw_sph, (void*)c->d_lw_orig, (void*)c->d_cnodes, (void*)c->d_cidx, (void*)c->d_direct})
     if (p) (void)hipFree(p);
-  if (c->d_cnodes) (void)hipFree(c->d_cnodes);
-  if (c->d_cidx) (void)hipFree(c->d_cidx);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->done) (void)hipEventDestroy(c->done);
-  if (c->d_direct) (void)hipFree(c->d_direct);
+  for (hipEvent_t e : {c->ev0, c->ev1, c->done})
+    if (e) (void)hipEventDestroy(e);
   for (rtp_context::ViewTable& t : c->view_tables) {  // (drained above: no launch reads them any more)
     if (t.host) (void)hipHostFree(t.host);
     if (t.dev) (void)hipFree(t.dev);
@@ -638,42 +598,63 @@ void rtp_destroy(rtp_context* c) {
   delete c;
 }
 
-// extract + buildBVH (MapperPathTracer.cxx:178-197, 437-449) and the light
-// coupling of the constructor (:141-148).  Quads that repeat an earlier quad
+}  // extern "C"
+
+// rtp_set_scene in steps: extract + buildBVH (MapperPathTracer.cxx:178-197,
+// 437-449) and the light coupling of the constructor (:141-148).  Every step
+// but the last works on the host only and may refuse the description; the
+// upload then replaces the context's scene.
+namespace {
+
+// what the steps hand on
+struct SceneBuild {
+  std::unique_ptr<rtp::DevScene> h{new rtp::DevScene()};  // the host image of the device scene
+  std::vector<int> kept;                                   // reference index of each kept quad
+  float blo[3], bhi[3];                                    // the quads' shape bounds (-direct mode)
+  std::vector<rtp::DevSphere> sph;
+  bool use_bvh = false, gpu_build = false;
+  float bvh_reach = 0.f;
+  std::vector<rtp::BvhNode> nodes;  // the host-built sphere BVH: 8 octant copies, and its leaf order's records
+  std::vector<rtp::DevSphereG> geom;
+  // the LDS walk's tree (kLdsWalkLeaf) in BvhNode form, its leaf order and size
+  std::vector<rtp::BvhNode> lw_nodes;
+  std::vector<int32_t> lw_order;
+  int lw_per_oct = 0;
+};
+
+bool pt_ok(const rtp_scene_desc* s, int32_t id) { return id >= 0 && id < s->n_points; }
+bool mat_ok(const rtp_scene_desc* s, int32_t m) {
+  return m >= 0 && m < s->n_mat && s->mat_type[m] >= 0 && s->mat_type[m] <= 2;
+}
+bool tex_ok(const rtp_scene_desc* s, int32_t t) {
+  return t >= 0 && t < s->n_tex_type && s->tex_type[t] >= 0 && s->tex_type[t] < s->n_tex;
+}
+
+// The quads: validated, de-duplicated, grouped by kind, with the prefilter
+// tables and the -direct mode's bounds.  Quads that repeat an earlier quad
 // bit-for-bit (same vertices in the same order, same material and texture --
 // buildBox emits two such pairs per box, CornellBox.cpp:114-137) are dropped:
 // under the strict '<' closest test the later copy can never win, so the hit
 // record is unchanged.
-rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
-  if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: NULL argument");
+rtp_status scene_quads(const rtp_scene_desc* s, SceneBuild& B) {
   if (s->n_points <= 0 || !s->points) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: no points");
   if (s->n_quads < 0 || s->n_spheres < 0 || s->n_spheres > rtp::kMaxSpheresBvh)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: bad primitive counts");
   if (s->n_spheres < 1)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: the light sphere radius is SphereRadii[0]; need >= 1 sphere");
-  auto pt_ok = [&](int32_t id) { return id >= 0 && id < s->n_points; };
-  auto mat_ok = [&](int32_t m) { return m >= 0 && m < s->n_mat && s->mat_type[m] >= 0 && s->mat_type[m] <= 2; };
-  auto tex_ok = [&](int32_t t) {
-    return t >= 0 && t < s->n_tex_type && s->tex_type[t] >= 0 && s->tex_type[t] < s->n_tex;
-  };
-  rtp::DevScene* h = new rtp::DevScene();
+  rtp::DevScene* h = B.h.get();
   std::memset(h, 0, sizeof(*h));
   // (after the memset: every octant its own walk order -- the device LBVH
   // build keeps all 8; the host SAH build may narrow it, RTP_BVH_OCT_MASK)
   h->oct_mask = 7;
-  std::vector<int> kept;
+  std::vector<int>& kept = B.kept;
   std::vector<rtp::DevQuad> built;
   for (int q = 0; q < s->n_quads; q++) {
     const int32_t* id = s->quad_points + 4 * q;
     for (int k = 0; k < 4; k++)
-      if (!pt_ok(id[k])) {
-        delete h;
-        return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: quad point id out of range");
-      }
-    if (!mat_ok(s->quad_mat[q]) || !tex_ok(s->quad_tex[q])) {
-      delete h;
+      if (!pt_ok(s, id[k])) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: quad point id out of range");
+    if (!mat_ok(s, s->quad_mat[q]) || !tex_ok(s, s->quad_tex[q]))
       return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: quad material/texture index out of range");
-    }
     bool dup = false;
     for (int j : kept) {
       const int32_t* jd = s->quad_points + 4 * j;
@@ -685,10 +666,8 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
       }
     }
     if (dup) continue;
-    if ((int)kept.size() >= rtp::kMaxQuads) {
-      delete h;
+    if ((int)kept.size() >= rtp::kMaxQuads)
       return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: too many distinct quads");
-    }
     rtp::DevQuad Q;
     fill_quad(Q, ld(s->points + 3 * id[0]), ld(s->points + 3 * id[1]), ld(s->points + 3 * id[2]),
               ld(s->points + 3 * id[3]));
@@ -714,24 +693,23 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
         }
     }
     h->kind_begin[rtp::kQuadKinds] = pos;
-    if (const char* v = getenv("RTP_VERBOSE")) {
-      if (v[0] == '1') {
-        fprintf(stderr, "rtp: %d quads by scan group (kind: count / exact parallelograms):", pos);
-        for (int g = 0; g < rtp::kQuadKinds; g++) {
-          int np = 0;
-          for (int i = h->kind_begin[g]; i < h->kind_begin[g + 1]; i++) np += h->quads[i].para ? 1 : 0;
-          fprintf(stderr, " %d: %d/%d", (g + 1) % rtp::kQuadKinds, h->kind_begin[g + 1] - h->kind_begin[g], np);
-        }
-        fprintf(stderr, "\n");
+    if (env_is("RTP_VERBOSE", '1')) {
+      fprintf(stderr, "rtp: %d quads by scan group (kind: count / exact parallelograms):", pos);
+      for (int g = 0; g < rtp::kQuadKinds; g++) {
+        int np = 0;
+        for (int i = h->kind_begin[g]; i < h->kind_begin[g + 1]; i++) np += h->quads[i].para ? 1 : 0;
+        fprintf(stderr, " %d: %d/%d", (g + 1) % rtp::kQuadKinds, h->kind_begin[g + 1] - h->kind_begin[g], np);
       }
+      fprintf(stderr, "\n");
     }
   }
   setup_prefilter(h, s, kept);
   h->n_quads = (int32_t)kept.size();
-  // the -direct mode's inputs: kept quad -> reference index, and the shape
-  // bounds (union of the quads' padded AABBs, AABBSurface.h:36-78)
-  std::vector<int32_t> kept_ref(kept.begin(), kept.end());
-  float blo[3] = {INFINITY, INFINITY, INFINITY}, bhi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  // the -direct mode's shape bounds (union of the quads' padded AABBs,
+  // AABBSurface.h:36-78)
+  float* blo = B.blo;
+  float* bhi = B.bhi;
+  for (int k = 0; k < 3; k++) blo[k] = INFINITY, bhi[k] = -INFINITY;
   for (int q = 0; q < s->n_quads; q++) {
     const int32_t* id = s->quad_points + 4 * q;
     float mn[3], mx[3];
@@ -751,13 +729,17 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
       bhi[k] = std::max(bhi[k], mx[k]);
     }
   }
-  std::vector<rtp::DevSphere> sph(s->n_spheres);
+  return RTP_OK;
+}
+
+// The sphere records, whether they get a BVH, its pad's reach and its builder.
+rtp_status scene_spheres(const rtp_scene_desc* s, SceneBuild& B) {
+  std::vector<rtp::DevSphere>& sph = B.sph;
+  sph.resize(s->n_spheres);
   for (int k = 0; k < s->n_spheres; k++) {
-    if (!pt_ok(s->sphere_point[k]) || !mat_ok(s->sphere_mat[k]) || !tex_ok(s->sphere_tex[k]) ||
-        !(s->sphere_radius[k] > 0.0f)) {
-      delete h;
+    if (!pt_ok(s, s->sphere_point[k]) || !mat_ok(s, s->sphere_mat[k]) || !tex_ok(s, s->sphere_tex[k]) ||
+        !(s->sphere_radius[k] > 0.0f))
       return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: sphere index or radius out of range");
-    }
     rtp::DevSphere& S = sph[k];
     std::memset(&S, 0, sizeof(S));
     st(S.c, ld(s->points + 3 * s->sphere_point[k]));
@@ -766,11 +748,11 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     S.mt = s->mat_type[s->sphere_mat[k]];
     st(S.alb, ld(s->tex_rgb + 3 * s->tex_type[s->sphere_tex[k]]));
   }
-  const bool use_bvh = s->n_spheres >= rtp::kBvhMinSpheres;
+  const bool use_bvh = B.use_bvh = s->n_spheres >= rtp::kBvhMinSpheres;
   // The reach of the sphere boxes' pad (rtp_layout.hpp bvh_sphere_pad):
   // kBvhReachFactor diagonals of the scene's bounding box -- every quad
   // vertex, every sphere's c -+ r.
-  float bvh_reach = 0.f;
+  float& bvh_reach = B.bvh_reach;
   if (use_bvh) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (int q = 0; q < s->n_quads; q++)
@@ -787,21 +769,31 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
   // which builder makes the sphere BVH: the host's binned SAH (better trees,
   // O(n log n) on one core) or the device LBVH (rtp_bvh_gpu.hip) for large
   // scenes; RTP_BVH_BUILD=host|gpu overrides
-  bool gpu_build = use_bvh && s->n_spheres >= rtp::kBvhGpuMinSpheres;
+  bool& gpu_build = B.gpu_build;
+  gpu_build = use_bvh && s->n_spheres >= rtp::kBvhGpuMinSpheres;
   if (const char* bb = getenv("RTP_BVH_BUILD")) {
     if (!std::strcmp(bb, "gpu")) gpu_build = use_bvh;
     if (!std::strcmp(bb, "host")) gpu_build = false;
   }
-  std::vector<rtp::BvhNode> nodes;
-  std::vector<rtp::DevSphereG> geom;
-  // the LDS walk's tree (kLdsWalkLeaf) in BvhNode form, its leaf order and size
-  std::vector<rtp::BvhNode> lw_nodes;
-  std::vector<int32_t> lw_order;
-  int lw_per_oct = 0;
-  if (!use_bvh) {
+  return RTP_OK;
+}
+
+// Where the spheres go: into the scene itself (few), or behind a BVH built on
+// the device at upload (many) or here -- the global walk's tree and, opt-in,
+// the LDS walk's.
+void scene_sphere_bvh(const rtp_scene_desc* s, SceneBuild& B) {
+  rtp::DevScene* h = B.h.get();
+  const std::vector<rtp::DevSphere>& sph = B.sph;
+  const float bvh_reach = B.bvh_reach;
+  std::vector<rtp::BvhNode>& nodes = B.nodes;
+  std::vector<rtp::DevSphereG>& geom = B.geom;
+  std::vector<rtp::BvhNode>& lw_nodes = B.lw_nodes;
+  std::vector<int32_t>& lw_order = B.lw_order;
+  int& lw_per_oct = B.lw_per_oct;
+  if (!B.use_bvh) {
     for (int k = 0; k < s->n_spheres; k++) h->spheres[k] = sph[k];
-  } else if (gpu_build) {
-    h->n_nodes = 2 * s->n_spheres - 1;  // nodes and sphere records are built on the device below
+  } else if (B.gpu_build) {
+    h->n_nodes = 2 * s->n_spheres - 1;  // nodes and sphere records are built on the device (scene_upload)
   } else {
     std::vector<BvhPrim> P(s->n_spheres);
     for (int k = 0; k < s->n_spheres; k++) {
@@ -845,8 +837,7 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     // global walk over the leaves-of-1 tree 186 -- the LDS copy saves 7% of the
     // texture-path gathers' cost, the bigger leaves it needs to fit cost 88%
     // (10 exact sphere tests per ray instead of 4: DESIGN.md 4.2).
-    const char* le = getenv("RTP_BVH_LDS");
-    if (le && le[0] == '1') {
+    if (env_is("RTP_BVH_LDS", '1')) {
       std::vector<BvhPrim> P2 = P0;
       std::vector<TNode> tree2;
       bvh_build(P2, 0, s->n_spheres, tree2, lw_order, rtp::kLdsWalkLeaf);
@@ -874,17 +865,17 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
     h->n_nodes = (int32_t)per_oct;
   }
   h->n_spheres = s->n_spheres;
-  // lights (MapperPathTracer.cxx:141-148): light quad = light_box_pointids[1..4]
+}
+
+// lights (MapperPathTracer.cxx:141-148): light quad = light_box_pointids[1..4];
+// the glass constants and the `which` thresholds
+rtp_status scene_lights(const rtp_scene_desc* s, SceneBuild& B) {
+  rtp::DevScene* h = B.h.get();
   const int32_t* lq = s->light_quad_points;
   for (int k = 0; k < 4; k++)
-    if (!pt_ok(lq[k])) {
-      delete h;
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light quad point id out of range");
-    }
-  if (!pt_ok(s->light_sphere_point)) {
-    delete h;
+    if (!pt_ok(s, lq[k])) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light quad point id out of range");
+  if (!pt_ok(s, s->light_sphere_point))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light sphere point id out of range");
-  }
   v3 q = ld(s->points + 3 * lq[0]), r = ld(s->points + 3 * lq[1]), ss = ld(s->points + 3 * lq[2]),
      t = ld(s->points + 3 * lq[3]);
   fill_quad(h->light.quad, q, r, ss, t);
@@ -911,102 +902,134 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
   }
   h->which_t1 = which_threshold(2);
   h->which_t2 = which_threshold(3);
-  hipError_t e = hipSetDevice(c->device);
-  if (c->pending) {  // a queued render may still read the old scene
-    if (e == hipSuccess) e = hipEventSynchronize(c->done);
-    c->pending = false;
+  return RTP_OK;
+}
+
+#define UPLOAD_TRY(expr) HIP_TRY_AS("rtp_set_scene upload", expr)
+
+// the sphere BVH built on the device (rtp_bvh_gpu.hip) from centres and radii
+rtp_status upload_bvh_gpu(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) {
+  rtp::DevScene* h = B.h.get();
+  const std::vector<rtp::DevSphere>& sph = B.sph;
+  const int n = s->n_spheres;
+  std::vector<float4> cr(n);
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int k = 0; k < n; k++) {
+    cr[k] = make_float4(sph[k].c[0], sph[k].c[1], sph[k].c[2], sph[k].r);
+    for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], sph[k].c[a]), hi[a] = std::max(hi[a], sph[k].c[a]);
   }
+  DevBufs tmp;
+  float4* d_cr = nullptr;
+  UPLOAD_TRY(hipMalloc(&c->d_nodes, (size_t)8 * h->n_nodes * sizeof(rtp::BvhNode)));
+  UPLOAD_TRY(hipMalloc(&c->d_sph_geom, (size_t)n * sizeof(rtp::DevSphereG)));
+  UPLOAD_TRY(hipMalloc(&c->d_sph_all, sph.size() * sizeof(rtp::DevSphere)));
+  UPLOAD_TRY(tmp.get(&d_cr, (size_t)n * sizeof(float4), cr.data()));
+  UPLOAD_TRY(rtp_build_bvh_gpu(d_cr, n, make_float3(lo[0], lo[1], lo[2]),
+                               make_float3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]), B.bvh_reach, c->d_nodes,
+                               c->d_sph_geom, nullptr));
+  UPLOAD_TRY(hipMemcpy(c->d_sph_all, sph.data(), sph.size() * sizeof(rtp::DevSphere), hipMemcpyHostToDevice));
+  return RTP_OK;
+}
+
+// the host-built trees: the global walk's and, when it was built, the LDS walk's
+rtp_status upload_bvh_host(rtp_context* c, SceneBuild& B) {
+  rtp::DevScene* h = B.h.get();
+  const std::vector<rtp::DevSphere>& sph = B.sph;
+  UPLOAD_TRY(hipMalloc(&c->d_nodes, B.nodes.size() * sizeof(rtp::BvhNode)));
+  UPLOAD_TRY(hipMalloc(&c->d_sph_geom, B.geom.size() * sizeof(rtp::DevSphereG)));
+  UPLOAD_TRY(hipMalloc(&c->d_sph_all, sph.size() * sizeof(rtp::DevSphere)));
+  UPLOAD_TRY(hipMemcpy(c->d_nodes, B.nodes.data(), B.nodes.size() * sizeof(rtp::BvhNode), hipMemcpyHostToDevice));
+  UPLOAD_TRY(hipMemcpy(c->d_sph_geom, B.geom.data(), B.geom.size() * sizeof(rtp::DevSphereG), hipMemcpyHostToDevice));
+  UPLOAD_TRY(hipMemcpy(c->d_sph_all, sph.data(), sph.size() * sizeof(rtp::DevSphere), hipMemcpyHostToDevice));
+  if (B.lw_per_oct <= 0) return RTP_OK;
+  // the LDS walk's tree: compacted like the global one
+  const int64_t total = (int64_t)8 * B.lw_per_oct, ns = (int64_t)B.lw_order.size();
+  std::vector<float> lsph(4 * ns);
+  for (int64_t j = 0; j < ns; j++) {
+    const rtp::DevSphere& S = sph[B.lw_order[j]];
+    lsph[4 * j] = S.c[0], lsph[4 * j + 1] = S.c[1], lsph[4 * j + 2] = S.c[2], lsph[4 * j + 3] = S.rr;
+  }
+  DevBufs tmp;
+  rtp::BvhNode* d_tmp = nullptr;
+  UPLOAD_TRY(tmp.get(&d_tmp, (size_t)total * sizeof(rtp::BvhNode)));
+  UPLOAD_TRY(hipMalloc(&c->d_lw_nodes, (size_t)total * 16));
+  UPLOAD_TRY(hipMalloc(&c->d_lw_cidx, (size_t)total * sizeof(int32_t)));
+  UPLOAD_TRY(hipMalloc(&c->d_lw_sph, (size_t)ns * 16));
+  UPLOAD_TRY(hipMalloc(&c->d_lw_orig, (size_t)ns * sizeof(int32_t)));
+  UPLOAD_TRY(hipMemcpy(d_tmp, B.lw_nodes.data(), (size_t)total * sizeof(rtp::BvhNode), hipMemcpyHostToDevice));
+  UPLOAD_TRY(hipMemcpy(c->d_lw_sph, lsph.data(), (size_t)ns * 16, hipMemcpyHostToDevice));
+  UPLOAD_TRY(hipMemcpy(c->d_lw_orig, B.lw_order.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice));
+  UPLOAD_TRY(rtp_compact_bvh(d_tmp, total, c->d_lw_nodes, c->d_lw_cidx, nullptr));
+  h->lw_nodes = c->d_lw_nodes;
+  h->lw_cidx = c->d_lw_cidx;
+  h->lw_sph = c->d_lw_sph;
+  h->lw_orig = c->d_lw_orig;
+  h->n_lw_nodes = B.lw_per_oct;
+  h->n_lw_sph = (int32_t)ns;
+  return RTP_OK;
+}
+
+// Replace the context's scene by the built one.  From the first freed buffer
+// until the new DevScene is on the device the context has no scene: an upload
+// that fails leaves it answering RTP_ERR_NO_SCENE (the arrays it did allocate
+// stay the context's and go with the next rtp_set_scene or rtp_destroy).
+rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) {
+  rtp::DevScene* h = B.h.get();
+  UPLOAD_TRY(hipSetDevice(c->device));
+  if (c->pending) {  // a queued render may still read the old scene
+    const hipError_t e = hipEventSynchronize(c->done);
+    c->pending = false;
+    UPLOAD_TRY(e);
+  }
+  c->has_scene = false;
+  c->use_bvh = false;
+  c->lw_bytes = 0;
+  c->oct_mask = 0;
   for (void** p : {(void**)&c->d_nodes, (void**)&c->d_sph_geom, (void**)&c->d_sph_all, (void**)&c->d_cnodes,
                    (void**)&c->d_cidx, (void**)&c->d_lw_nodes, (void**)&c->d_lw_cidx, (void**)&c->d_lw_sph,
                    (void**)&c->d_lw_orig})
-    if (*p && e == hipSuccess) {
-      e = hipFree(*p);
+    if (*p) {
+      const hipError_t e = hipFree(*p);
       *p = nullptr;
+      UPLOAD_TRY(e);
     }
-  if (use_bvh && gpu_build && e == hipSuccess) {
-    const int n = s->n_spheres;
-    std::vector<float4> cr(n);
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = 0; k < n; k++) {
-      cr[k] = make_float4(sph[k].c[0], sph[k].c[1], sph[k].c[2], sph[k].r);
-      for (int a = 0; a < 3; a++) lo[a] = std::min(lo[a], sph[k].c[a]), hi[a] = std::max(hi[a], sph[k].c[a]);
-    }
-    float4* d_cr = nullptr;
-    e = hipMalloc(&c->d_nodes, (size_t)8 * h->n_nodes * sizeof(rtp::BvhNode));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sph_geom, (size_t)n * sizeof(rtp::DevSphereG));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sph_all, sph.size() * sizeof(rtp::DevSphere));
-    if (e == hipSuccess) e = hipMalloc(&d_cr, (size_t)n * sizeof(float4));
-    if (e == hipSuccess) e = hipMemcpy(d_cr, cr.data(), (size_t)n * sizeof(float4), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = rtp_build_bvh_gpu(d_cr, n, make_float3(lo[0], lo[1], lo[2]),
-                            make_float3(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]), bvh_reach, c->d_nodes,
-                            c->d_sph_geom, nullptr);
-    if (d_cr) (void)hipFree(d_cr);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_sph_all, sph.data(), sph.size() * sizeof(rtp::DevSphere), hipMemcpyHostToDevice);
+  if (B.use_bvh) {
+    RTP_TRY(B.gpu_build ? upload_bvh_gpu(c, s, B) : upload_bvh_host(c, B));
     h->nodes = c->d_nodes;
     h->sph_geom = c->d_sph_geom;
     h->sph_all = c->d_sph_all;
-  } else if (use_bvh && e == hipSuccess) {
-    e = hipMalloc(&c->d_nodes, nodes.size() * sizeof(rtp::BvhNode));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sph_geom, geom.size() * sizeof(rtp::DevSphereG));
-    if (e == hipSuccess) e = hipMalloc(&c->d_sph_all, sph.size() * sizeof(rtp::DevSphere));
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_nodes, nodes.data(), nodes.size() * sizeof(rtp::BvhNode), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_sph_geom, geom.data(), geom.size() * sizeof(rtp::DevSphereG), hipMemcpyHostToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(c->d_sph_all, sph.data(), sph.size() * sizeof(rtp::DevSphere), hipMemcpyHostToDevice);
-    h->nodes = c->d_nodes;
-    h->sph_geom = c->d_sph_geom;
-    h->sph_all = c->d_sph_all;
-    if (e == hipSuccess && lw_per_oct > 0) {  // the LDS walk's tree: compacted like the global one
-      const int64_t total = (int64_t)8 * lw_per_oct, ns = (int64_t)lw_order.size();
-      std::vector<float> lsph(4 * ns);
-      for (int64_t j = 0; j < ns; j++) {
-        const rtp::DevSphere& S = sph[lw_order[j]];
-        lsph[4 * j] = S.c[0], lsph[4 * j + 1] = S.c[1], lsph[4 * j + 2] = S.c[2], lsph[4 * j + 3] = S.rr;
-      }
-      rtp::BvhNode* d_tmp = nullptr;
-      e = hipMalloc(&d_tmp, (size_t)total * sizeof(rtp::BvhNode));
-      if (e == hipSuccess) e = hipMalloc(&c->d_lw_nodes, (size_t)total * 16);
-      if (e == hipSuccess) e = hipMalloc(&c->d_lw_cidx, (size_t)total * sizeof(int32_t));
-      if (e == hipSuccess) e = hipMalloc(&c->d_lw_sph, (size_t)ns * 16);
-      if (e == hipSuccess) e = hipMalloc(&c->d_lw_orig, (size_t)ns * sizeof(int32_t));
-      if (e == hipSuccess)
-        e = hipMemcpy(d_tmp, lw_nodes.data(), (size_t)total * sizeof(rtp::BvhNode), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = hipMemcpy(c->d_lw_sph, lsph.data(), (size_t)ns * 16, hipMemcpyHostToDevice);
-      if (e == hipSuccess)
-        e = hipMemcpy(c->d_lw_orig, lw_order.data(), (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = rtp_compact_bvh(d_tmp, total, c->d_lw_nodes, c->d_lw_cidx, nullptr);
-      if (d_tmp) (void)hipFree(d_tmp);
-      h->lw_nodes = c->d_lw_nodes;
-      h->lw_cidx = c->d_lw_cidx;
-      h->lw_sph = c->d_lw_sph;
-      h->lw_orig = c->d_lw_orig;
-      h->n_lw_nodes = lw_per_oct;
-      h->n_lw_sph = (int32_t)ns;
-    }
-  }
-  if (use_bvh && e == hipSuccess) {  // the walks' compact copy of the octant arrays
+    // the walks' compact copy of the octant arrays
     const int64_t total = (int64_t)8 * h->n_nodes;
-    e = hipMalloc(&c->d_cnodes, (size_t)total * 16);
-    if (e == hipSuccess) e = hipMalloc(&c->d_cidx, (size_t)total * sizeof(int32_t));
-    if (e == hipSuccess) e = rtp_compact_bvh(c->d_nodes, total, c->d_cnodes, c->d_cidx, nullptr);
+    UPLOAD_TRY(hipMalloc(&c->d_cnodes, (size_t)total * 16));
+    UPLOAD_TRY(hipMalloc(&c->d_cidx, (size_t)total * sizeof(int32_t)));
+    UPLOAD_TRY(rtp_compact_bvh(c->d_nodes, total, c->d_cnodes, c->d_cidx, nullptr));
     h->cnodes = c->d_cnodes;
     h->cidx = c->d_cidx;
   }
-  if (e == hipSuccess) e = hipMemcpy(c->d_scene, h, sizeof(*h), hipMemcpyHostToDevice);
+  UPLOAD_TRY(hipMemcpy(c->d_scene, h, sizeof(*h), hipMemcpyHostToDevice));
   c->lw_bytes = h->n_lw_nodes > 0 ? 16 * (8 * h->n_lw_nodes + h->n_lw_sph) : 0;
-  c->use_bvh = use_bvh;
-  c->oct_mask = use_bvh ? h->oct_mask : 0;  // (read before the host copy is freed)
-  delete h;
-  if (e != hipSuccess) return hip_fail(e, "rtp_set_scene upload");
-  c->kept_quads = std::move(kept_ref);
+  c->use_bvh = B.use_bvh;
+  c->oct_mask = B.use_bvh ? h->oct_mask : 0;
+  c->kept_quads.assign(B.kept.begin(), B.kept.end());  // the -direct mode's kept quad -> reference index
   c->n_ref_quads = s->n_quads;
-  for (int k = 0; k < 3; k++) c->quad_lo[k] = blo[k], c->quad_hi[k] = bhi[k];
+  for (int k = 0; k < 3; k++) c->quad_lo[k] = B.blo[k], c->quad_hi[k] = B.bhi[k];
   c->has_scene = true;
   return RTP_OK;
+}
+#undef UPLOAD_TRY
+
+}  // namespace
+
+extern "C" {
+
+rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
+  if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: NULL argument");
+  SceneBuild B;
+  RTP_TRY(scene_quads(s, B));
+  RTP_TRY(scene_spheres(s, B));
+  scene_sphere_bvh(s, B);
+  RTP_TRY(scene_lights(s, B));
+  return scene_upload(c, s, B);
 }
 
 }  // extern "C"
@@ -1019,9 +1042,8 @@ void camera_setup(const rtp_camera* cam, int32_t nx, int32_t ny, rtp::DevCamera*
   if (!(up.x == 0.f && up.y == 1.f && up.z == 0.f)) up = normalize(up);  // SetUp (Camera.cxx:767-776)
   v3 pos = ld(cam->position);
   v3 look = normalize(sub(ld(cam->look_at), pos));  // Camera.cxx:908-909
-  const float pi_180f = 0.01745329251994329577f;    // vtkm::Pi_180f()
-  float thx = tanf((cam->fov_y_deg * pi_180f) * .5f);
-  float thy = tanf((cam->fov_y_deg * pi_180f) * .5f);
+  float thx = tanf((cam->fov_y_deg * kPi180f) * .5f);
+  float thy = tanf((cam->fov_y_deg * kPi180f) * .5f);
   v3 u = normalize(cross(look, up));
   v3 v = normalize(cross(u, look));
   st(out->eye, pos);
@@ -1033,11 +1055,7 @@ void camera_setup(const rtp_camera* cam, int32_t nx, int32_t ny, rtp::DevCamera*
 rtp_status check_render_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                              int32_t depth) {
   if (!c || !cam) return fail(RTP_ERR_INVALID_ARGUMENT, "render: NULL argument");
-  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "render: rtp_set_scene was not called");
-  if (nx <= 0 || ny <= 0) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera width/height must be greater than zero.");
-  if ((int64_t)nx * ny > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render: canvas too large");
-  if (!(cam->fov_y_deg > 0)) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera feild of view must be greater than zero.");
-  if (cam->fov_y_deg > 180) return fail(RTP_ERR_INVALID_ARGUMENT, "Camera feild of view must be less than 180.");
+  RTP_TRY(check_canvas_camera(c, cam, nx, ny, "render"));
   if (spp < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "render: samplecount must be >= 0");
   // depthcount < 1 makes the reference read emitted[(depth-1)*N] out of range
   // (MapperPathTracer.cxx:328-331); rejected here.
@@ -1052,8 +1070,7 @@ rtp_status check_render_args(rtp_context* c, const rtp_camera* cam, int32_t nx, 
 
 rtp_status ensure_hist(rtp_context* c, size_t bytes) {
   if (bytes <= c->hist_bytes) return RTP_OK;
-  rtp_status rs = drain(c);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(drain(c));
   if (c->d_hist) HIP_TRY(hipFree(c->d_hist));
   c->d_hist = nullptr;
   c->hist_bytes = 0;
@@ -1062,164 +1079,166 @@ rtp_status ensure_hist(rtp_context* c, size_t bytes) {
   return RTP_OK;
 }
 
-rtp_status launch(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth,
-                  uint32_t seed_base, int64_t pixel_begin, int64_t npix, const int64_t* d_ids, float* d_out,
-                  uint32_t* d_seed, uint32_t* d_live, hipStream_t stream, double* kernel_ms,
-                  const int32_t* tile = nullptr, const int32_t* d_wave_begin = nullptr, int plan_waves = 0,
-                  const rtp::DevView* d_views = nullptr, bool resume = false, float* d_m2 = nullptr) {
+// One launch of the render kernel: every caller names the fields it uses.
+struct RenderJob {
+  const rtp_camera* cam = nullptr;        // the camera, or
+  const rtp::DevView* d_views = nullptr;  // batched views: cameras and seed bases in a device table
+  int32_t nx = 0, ny = 0, spp = 0, depth = 0;
+  uint32_t seed_base = 0;
+  int64_t pixel_begin = 0, npix = 0;  // the entries: a range, or
+  const int64_t* d_ids = nullptr;     // a pixel list
+  float* d_out = nullptr;
+  uint32_t *d_seed = nullptr, *d_live = nullptr;  // optional final seeds and live-bounce counts
+  hipStream_t stream = nullptr;
+  const int32_t* tile = nullptr;          // optional tile deal {tiles per row, world, rank}
+  const int32_t* d_wave_begin = nullptr;  // optional wave plan of plan_waves waves
+  int plan_waves = 0;
+  bool resume = false;  // a pass over a render state: d_out, d_seed, d_live, d_m2 are read and updated
+  float* d_m2 = nullptr;
+  double* kernel_ms = nullptr;  // where the kernel time goes (the call then waits for it)
+};
+
+// how a job runs on the context's scene
+struct LaunchPlan {
+  int variant = 2, waves = 0, bvh = 0;  // bvh: the sphere walk (plan_launch)
+  int64_t lanes = 0;                    // history lanes
+  bool stats_on = false, dbg = false;   // RTP_DEBUG_STATS=1: the diagnostics build; 1 or 2: per-wave counters
+};
+
+rtp_status plan_launch(rtp_context* c, const RenderJob& j, LaunchPlan& pl) {
   // the kernels index a launch's entries with 32-bit integers
-  if (npix > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render: more than 2^31-1 pixels in one launch");
+  if (j.npix > INT32_MAX) return fail(RTP_ERR_INVALID_ARGUMENT, "render: more than 2^31-1 pixels in one launch");
   HIP_TRY(hipSetDevice(c->device));
-  rtp::KParams p{};
-  if (tile) p.tile_tx = tile[0], p.tile_world = tile[1], p.tile_rank = tile[2];
-  // (batched views: the cameras and seed bases are in the device table, cam is null)
-  if (d_views) p.views = d_views;
-  else camera_setup(cam, nx, ny, &p.cam);
-  p.nx = nx, p.ny = ny, p.spp = spp, p.depth = depth;
-  p.seed_base = seed_base;
-  p.pixel_begin = pixel_begin;
-  p.pixel_ids = d_ids;
-  p.npix = npix;
-  p.out = d_out;
-  p.seed_out = d_seed;
-  p.live_out = d_live;
-  p.resume = resume ? 1 : 0;  // a pass over a render state: d_out, d_seed, d_live, d_m2 are read and updated
-  p.m2 = d_m2;
-  int variant = 2, waves = 0;
   // the sphere BVH's walk: 2 out of LDS when the tree fits (rtp_render_pool_lds),
   // 1 the global threaded walk (also for the diagnostics build and wave plans)
-  const char* stats_env = getenv("RTP_DEBUG_STATS");
-  const bool stats_on = stats_env && stats_env[0] == '1';
+  const char stats_env = env_char("RTP_DEBUG_STATS");
+  pl.stats_on = stats_env == '1';
+  pl.dbg = stats_env == '1' || stats_env == '2';  // 2: timestamps in the production kernel
   // (a resume pass has no LDS-walk instance: the global walk, same results)
-  const int bvh = !c->use_bvh ? 0 : (c->lw_bytes > 0 && !stats_on && !d_wave_begin && !resume) ? 2 : 1;
-  int64_t lanes = rtp_plan_history_lanes(npix, spp, bvh, &variant, &waves);
-  if (d_wave_begin) {  // a planned launch: the caller's waves
-    if (variant != 2 || c->use_bvh || tile)
+  pl.bvh = !c->use_bvh ? 0 : (c->lw_bytes > 0 && !pl.stats_on && !j.d_wave_begin && !j.resume) ? 2 : 1;
+  pl.lanes = rtp_plan_history_lanes(j.npix, j.spp, pl.bvh, &pl.variant, &pl.waves);
+  if (j.d_wave_begin) {  // a planned launch: the caller's waves
+    if (pl.variant != 2 || c->use_bvh || j.tile)
       return fail(RTP_ERR_INVALID_ARGUMENT, "render: a wave plan needs the pool kernel, no BVH, no tile deal");
-    waves = plan_waves;
-    lanes = (int64_t)plan_waves * 128;
+    pl.waves = j.plan_waves;
+    pl.lanes = (int64_t)j.plan_waves * 128;
   }
-  p.wave_begin = d_wave_begin;
   // more entries than the resident waves' pools hold: the resident waves
   // steal entries (RTP_STEAL=0: waves of 128 entries in generations)
-  if (variant == 2 && !d_wave_begin && !stats_on && spp > 0) {
-    const char* se = getenv("RTP_STEAL");
-    const int sw = (se && se[0] == '0') ? 0 : rtp_plan_steal(npix, bvh);
+  if (pl.variant == 2 && !j.d_wave_begin && !pl.stats_on && j.spp > 0) {
+    const int sw = env_is("RTP_STEAL", '0') ? 0 : rtp_plan_steal(j.npix, pl.bvh);
     if (sw > 0) {
-      waves = sw;
-      lanes = (int64_t)sw * 128;
+      pl.waves = sw;
+      pl.lanes = (int64_t)sw * 128;
     }
   }
-  // D rows per lane (row k of a light hit holds E_k), rounded up to 8 (a
-  // slot-major history pads each slot to whole 128-byte lines)
-  size_t hist_need = (size_t)((depth + 7) & ~7) * (size_t)lanes * 16;
-  rtp_status rs = ensure_hist(c, hist_need);
-  if (rs != RTP_OK) return rs;
-  p.hist = c->d_hist;
-  p.dbg = nullptr;
-  p.progress = c->d_progress;
-  if (variant == 2) {
-    const FfSnap ft = ff_tables(c->device, c->ff_policy, (uint64_t)npix * (uint64_t)spp);
-    for (int j = 0; j < rtp::kFfTables; j++) p.ff[j] = ft.t[j];
-    p.ffd = ft.direct, p.ffd_first = ft.d_first, p.ffd_count = ft.d_count;
-  }
-  if (c->pending) HIP_TRY(hipStreamWaitEvent(stream, c->done, 0));
-  HIP_TRY(hipMemsetAsync(c->d_progress, 0, 16, stream));  // [0] progress, [1] entries stolen (kSteal)
-  {
-    const char* e = getenv("RTP_DEBUG_STATS");
-    if (e && (e[0] == '1' || e[0] == '2') && variant == 2) {  // 2: timestamps in the production kernel
-      if (c->d_dbg) (void)hipFree(c->d_dbg);
-      c->d_dbg = nullptr;
-      HIP_TRY(hipMalloc(&c->d_dbg, (size_t)waves * rtp::kDbgCounters * 8));
-      HIP_TRY(hipMemsetAsync(c->d_dbg, 0, (size_t)waves * rtp::kDbgCounters * 8, stream));
-      c->dbg_waves = waves;
-      p.dbg = c->d_dbg;
-    }
-  }
-  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
-  HIP_TRY(rtp_launch_render(c->d_scene, &p, variant, waves, bvh, stream, c->lw_bytes));
-  HIP_TRY(hipEventRecord(c->done, stream));
-  c->pending = true;
-  if (kernel_ms) {
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *kernel_ms = ms;
-  }
+  pl.dbg = pl.dbg && pl.variant == 2;
   return RTP_OK;
 }
 
+rtp_status launch(rtp_context* c, const RenderJob& j) {
+  LaunchPlan pl;
+  RTP_TRY(plan_launch(c, j, pl));
+  rtp::KParams p{};
+  if (j.tile) p.tile_tx = j.tile[0], p.tile_world = j.tile[1], p.tile_rank = j.tile[2];
+  if (j.d_views) p.views = j.d_views;
+  else camera_setup(j.cam, j.nx, j.ny, &p.cam);
+  p.nx = j.nx, p.ny = j.ny, p.spp = j.spp, p.depth = j.depth;
+  p.seed_base = j.seed_base;
+  p.pixel_begin = j.pixel_begin, p.pixel_ids = j.d_ids, p.npix = j.npix;
+  p.out = j.d_out, p.seed_out = j.d_seed, p.live_out = j.d_live;
+  p.resume = j.resume ? 1 : 0, p.m2 = j.d_m2;
+  p.wave_begin = j.d_wave_begin;
+  // D rows per lane (row k of a light hit holds E_k), rounded up to 8 (a
+  // slot-major history pads each slot to whole 128-byte lines)
+  size_t hist_need = (size_t)((j.depth + 7) & ~7) * (size_t)pl.lanes * 16;
+  RTP_TRY(ensure_hist(c, hist_need));
+  p.hist = c->d_hist;
+  p.dbg = nullptr;
+  p.progress = c->d_progress;
+  if (pl.variant == 2) {
+    const FfSnap ft = ff_tables(c->device, c->ff_policy, (uint64_t)j.npix * (uint64_t)j.spp);
+    for (int k = 0; k < rtp::kFfTables; k++) p.ff[k] = ft.t[k];
+    p.ffd = ft.direct, p.ffd_first = ft.d_first, p.ffd_count = ft.d_count;
+  }
+  if (c->pending) HIP_TRY(hipStreamWaitEvent(j.stream, c->done, 0));
+  HIP_TRY(hipMemsetAsync(c->d_progress, 0, 16, j.stream));  // [0] progress, [1] entries stolen (kSteal)
+  if (pl.dbg) {
+    if (c->d_dbg) (void)hipFree(c->d_dbg);
+    c->d_dbg = nullptr;
+    HIP_TRY(hipMalloc(&c->d_dbg, (size_t)pl.waves * rtp::kDbgCounters * 8));
+    HIP_TRY(hipMemsetAsync(c->d_dbg, 0, (size_t)pl.waves * rtp::kDbgCounters * 8, j.stream));
+    c->dbg_waves = pl.waves;
+    p.dbg = c->d_dbg;
+  }
+  return timed_launch(c, j.stream, j.kernel_ms, true, [&]() -> rtp_status {
+    HIP_TRY(rtp_launch_render(c->d_scene, &p, pl.variant, pl.waves, pl.bvh, j.stream, c->lw_bytes));
+    return RTP_OK;
+  });
+}
+
 // host-buffer render of an optional pixel list (nullptr: contiguous range)
-rtp_status render_host(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth,
-                       uint32_t seed_base, const int64_t* ids, int64_t npix, float* rgba_out,
-                       const rtp_pixel_aux* aux, rtp_stats* stats) {
+rtp_status render_host(rtp_context* c, RenderJob j, const int64_t* ids, float* rgba_out, const rtp_pixel_aux* aux,
+                       rtp_stats* stats) {
   HIP_TRY(hipSetDevice(c->device));
-  if (npix == 0) {
-    if (stats) *stats = rtp_stats{};
+  if (j.npix == 0) {
+    fill_stats(stats, 0, 0);
     return RTP_OK;
   }
+  const size_t n = (size_t)j.npix;
+  DevBufs b;
+  HIP_TRY_AS("render: device buffers", b.get(&j.d_out, n * 16));
+  HIP_TRY_AS("render: device buffers", b.get(&j.d_live, n * 4));
+  if (aux && aux->final_seed) HIP_TRY_AS("render: device buffers", b.get(&j.d_seed, n * 4));
   int64_t* d_ids = nullptr;
-  float* d_out = nullptr;
-  uint32_t *d_seed = nullptr, *d_live = nullptr;
-  rtp_status rs = RTP_OK;
+  if (ids) HIP_TRY_AS("render: device buffers", b.get(&d_ids, n * 8, ids));
   double ms = 0;
-  std::vector<uint32_t> live(npix);
-  auto cleanup = [&]() {
-    if (d_ids) (void)hipFree(d_ids);
-    if (d_out) (void)hipFree(d_out);
-    if (d_seed) (void)hipFree(d_seed);
-    if (d_live) (void)hipFree(d_live);
-  };
-  hipError_t e = hipMalloc(&d_out, (size_t)npix * 16);
-  if (e == hipSuccess) e = hipMalloc(&d_live, (size_t)npix * 4);
-  if (e == hipSuccess && aux && aux->final_seed) e = hipMalloc(&d_seed, (size_t)npix * 4);
-  if (e == hipSuccess && ids) {
-    e = hipMalloc(&d_ids, (size_t)npix * 8);
-    if (e == hipSuccess) e = hipMemcpy(d_ids, ids, (size_t)npix * 8, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    cleanup();
-    return hip_fail(e, "render: device buffers");
-  }
-  rs = launch(c, cam, nx, ny, spp, depth, seed_base, 0, npix, d_ids, d_out, d_seed, d_live, nullptr, &ms);
-  if (rs == RTP_OK) {
-    e = hipMemcpy(rgba_out, d_out, (size_t)npix * 16, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, (size_t)npix * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d_seed) e = hipMemcpy(aux->final_seed, d_seed, (size_t)npix * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rs = hip_fail(e, "render: copy back");
-  }
-  cleanup();
-  if (rs != RTP_OK) return rs;
-  if (aux && aux->live_bounces) std::memcpy(aux->live_bounces, live.data(), (size_t)npix * 4);
-  if (stats) {
-    stats->samples = (uint64_t)npix * (uint64_t)spp;
-    uint64_t lb = 0, nan = 0;
-    for (int64_t i = 0; i < npix; i++) {
-      lb += live[i];
-      const float* px = rgba_out + 4 * i;
-      nan += (std::isnan(px[0]) || std::isnan(px[1]) || std::isnan(px[2])) ? 1 : 0;
-    }
-    stats->live_bounces = lb;
-    stats->nan_pixels = nan;
-    stats->kernel_ms = ms;
-  }
+  j.d_ids = d_ids, j.kernel_ms = &ms;
+  std::vector<uint32_t> live(n);
+  RTP_TRY(launch(c, j));
+  HIP_TRY_AS("render: copy back", DevBufs::back(rgba_out, j.d_out, n * 16));
+  HIP_TRY_AS("render: copy back", DevBufs::back(live.data(), j.d_live, n * 4));
+  HIP_TRY_AS("render: copy back", DevBufs::back(aux ? aux->final_seed : nullptr, j.d_seed, n * 4));
+  if (aux && aux->live_bounces) std::memcpy(aux->live_bounces, live.data(), n * 4);
+  fill_stats(stats, (uint64_t)j.npix * (uint64_t)j.spp, ms);
+  sum_stats(stats, rgba_out, live.data(), j.npix);
+  return RTP_OK;
+}
+
+// the job fields every render entry takes from its arguments
+RenderJob job_of(const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth, uint32_t seed_base) {
+  RenderJob j;
+  j.cam = cam, j.nx = nx, j.ny = ny, j.spp = spp, j.depth = depth, j.seed_base = seed_base;
+  return j;
+}
+// one more pass over a device render state (its seeds continue: no seed base)
+RenderJob resume_job(const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth,
+                     const rtp_render_state& st) {
+  RenderJob j = job_of(cam, nx, ny, spp, depth, 0u);
+  j.d_out = st.rgba, j.d_seed = st.seed, j.d_live = st.live_bounces, j.d_m2 = st.m2;
+  j.resume = true;
+  return j;
+}
+// the tail of a _device entry: the job on the caller's stream, timed when stats are asked for
+rtp_status launch_device(rtp_context* c, RenderJob& j, const rtp_pixel_aux* aux, void* hip_stream, rtp_stats* stats) {
+  double ms = 0;
+  if (aux) j.d_seed = aux->final_seed, j.d_live = aux->live_bounces;
+  j.stream = (hipStream_t)hip_stream;
+  j.kernel_ms = stats ? &ms : nullptr;
+  RTP_TRY(launch(c, j));
+  fill_stats(stats, (uint64_t)j.npix * (uint64_t)j.spp, ms);
   return RTP_OK;
 }
 
 // the checks of rtp_render_resume* before their pixel sets
 rtp_status check_resume_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                              int32_t depth, const rtp_render_state* st, const char* who) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (!st || !st->rgba || !st->seed)
     return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": state, state->rgba and state->seed are required");
-  auto is1 = [](const char* name) {
-    const char* e = getenv(name);
-    return e && e[0] == '1';
-  };
-  if (is1("RTP_KERNEL")) return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with RTP_KERNEL=1");
-  if (is1("RTP_DEBUG_STATS"))
+  if (env_is("RTP_KERNEL", '1'))
+    return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with RTP_KERNEL=1");
+  if (env_is("RTP_DEBUG_STATS", '1'))
     return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available with RTP_DEBUG_STATS=1");
   return RTP_OK;
 }
@@ -1230,48 +1249,42 @@ extern "C" {
 
 rtp_status rtp_render(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp, int32_t depth,
                       uint32_t seed_base, float* rgba_out, rtp_stats* stats) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (!rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render: rgba_out is NULL");
-  return render_host(c, cam, nx, ny, spp, depth, seed_base, nullptr, (int64_t)nx * ny, rgba_out, nullptr, stats);
+  RenderJob j = job_of(cam, nx, ny, spp, depth, seed_base);
+  j.npix = (int64_t)nx * ny;
+  return render_host(c, j, nullptr, rgba_out, nullptr, stats);
 }
 
 rtp_status rtp_render_pixels(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                              int32_t depth, uint32_t seed_base, const int64_t* pixel_ids, int64_t pixel_count,
                              float* rgba_out, const rtp_pixel_aux* aux, rtp_stats* stats) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (pixel_count < 0 || (pixel_count > 0 && (!pixel_ids || !rgba_out)))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_pixels: bad pixel list / output");
   const int64_t npx = (int64_t)nx * ny;
   for (int64_t i = 0; i < pixel_count; i++)
     if (pixel_ids[i] < 0 || pixel_ids[i] >= npx)
       return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_pixels: pixel id out of range");
-  return render_host(c, cam, nx, ny, spp, depth, seed_base, pixel_ids, pixel_count, rgba_out, aux, stats);
+  RenderJob j = job_of(cam, nx, ny, spp, depth, seed_base);
+  j.npix = pixel_count;
+  return render_host(c, j, pixel_ids, rgba_out, aux, stats);
 }
 
 rtp_status rtp_render_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                              int32_t depth, uint32_t seed_base, int64_t pixel_begin, int64_t pixel_count,
                              const int64_t* d_pixel_ids, float* d_rgba_out, const rtp_pixel_aux* aux,
                              void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (pixel_count < 0 || (pixel_count > 0 && !d_rgba_out))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_device: bad output");
   if (!d_pixel_ids && (pixel_begin < 0 || pixel_begin + pixel_count > (int64_t)nx * ny))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_device: pixel range outside the canvas");
   if (pixel_count == 0) return RTP_OK;
-  double ms = 0;
-  rs = launch(c, cam, nx, ny, spp, depth, seed_base, pixel_begin, pixel_count, d_pixel_ids, d_rgba_out,
-              aux ? aux->final_seed : nullptr, aux ? aux->live_bounces : nullptr, (hipStream_t)hip_stream,
-              stats ? &ms : nullptr);
-  if (rs == RTP_OK && stats) {
-    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
-    stats->live_bounces = 0;
-    stats->nan_pixels = 0;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RenderJob j = job_of(cam, nx, ny, spp, depth, seed_base);
+  j.pixel_begin = pixel_begin, j.npix = pixel_count, j.d_ids = d_pixel_ids;
+  j.d_out = d_rgba_out;
+  return launch_device(c, j, aux, hip_stream, stats);
 }
 
 // rtp_render_device with a wave plan (include/rtp.h).
@@ -1279,8 +1292,7 @@ rtp_status rtp_render_planned_device(rtp_context* c, const rtp_camera* cam, int3
                                      int32_t depth, uint32_t seed_base, int64_t pixel_begin, int64_t pixel_count,
                                      const int64_t* d_pixel_ids, const int32_t* d_wave_begin, int32_t n_waves,
                                      float* d_rgba_out, const rtp_pixel_aux* aux, void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (pixel_count <= 0 || !d_rgba_out || !d_wave_begin || n_waves <= 0 || n_waves > (1 << 24))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_planned_device: bad plan / output");
   if (!d_pixel_ids && (pixel_begin < 0 || pixel_begin + pixel_count > (int64_t)nx * ny))
@@ -1297,16 +1309,11 @@ rtp_status rtp_render_planned_device(rtp_context* c, const rtp_camera* cam, int3
       return fail(RTP_ERR_INVALID_ARGUMENT,
                   "rtp_render_planned_device: wave_begin must rise from 0 to pixel_count in steps of at most 128");
   }
-  double ms = 0;
-  rs = launch(c, cam, nx, ny, spp, depth, seed_base, pixel_begin, pixel_count, d_pixel_ids, d_rgba_out,
-              aux ? aux->final_seed : nullptr, aux ? aux->live_bounces : nullptr, (hipStream_t)hip_stream,
-              stats ? &ms : nullptr, nullptr, d_wave_begin, n_waves);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RenderJob j = job_of(cam, nx, ny, spp, depth, seed_base);
+  j.pixel_begin = pixel_begin, j.npix = pixel_count, j.d_ids = d_pixel_ids;
+  j.d_out = d_rgba_out;
+  j.d_wave_begin = d_wave_begin, j.plan_waves = n_waves;
+  return launch_device(c, j, aux, hip_stream, stats);
 }
 
 // rtp_render_device over the rank's tiles of a round-robin 16x16 tile deal
@@ -1318,8 +1325,7 @@ rtp_status rtp_render_planned_device(rtp_context* c, const rtp_camera* cam, int3
 rtp_status rtp_render_tiles_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                                    int32_t depth, uint32_t seed_base, int32_t rank, int32_t world, float* d_rgba_out,
                                    void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
   if (world < 1 || rank < 0 || rank >= world)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_tiles_device: rank outside [0, world)");
   const int64_t tx = (nx + 15) / 16, ty = (ny + 15) / 16;
@@ -1331,16 +1337,10 @@ rtp_status rtp_render_tiles_device(rtp_context* c, const rtp_camera* cam, int32_
   if (mine == 0) return RTP_OK;
   if (!d_rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_tiles_device: bad output");
   const int32_t tile[3] = {(int32_t)tx, world, rank};
-  double ms = 0;
-  rs = launch(c, cam, nx, ny, spp, depth, seed_base, 0, mine * 256, nullptr, d_rgba_out, nullptr, nullptr,
-              (hipStream_t)hip_stream, stats ? &ms : nullptr, tile);
-  if (rs == RTP_OK && stats) {
-    stats->samples = (uint64_t)mine * 256 * (uint64_t)spp;
-    stats->live_bounces = 0;
-    stats->nan_pixels = 0;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RenderJob j = job_of(cam, nx, ny, spp, depth, seed_base);
+  j.npix = mine * 256, j.tile = tile;
+  j.d_out = d_rgba_out;
+  return launch_device(c, j, nullptr, hip_stream, stats);
 }
 
 // One more pass of spp samples over a render state (include/rtp.h): the pool
@@ -1349,30 +1349,22 @@ rtp_status rtp_render_resume_device(rtp_context* c, const rtp_camera* cam, int32
                                     int32_t depth, int64_t pixel_begin, int64_t pixel_count,
                                     const int64_t* d_pixel_ids, const rtp_render_state* d_state, void* hip_stream,
                                     rtp_stats* stats) {
-  rtp_status rs = check_resume_args(c, cam, nx, ny, spp, depth, d_state, "rtp_render_resume_device");
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_resume_args(c, cam, nx, ny, spp, depth, d_state, "rtp_render_resume_device"));
   if (pixel_count < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume_device: pixel_count < 0");
   if (!d_pixel_ids && (pixel_begin < 0 || pixel_begin + pixel_count > (int64_t)nx * ny))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume_device: pixel range outside the canvas");
   if (stats) *stats = rtp_stats{};
   if (pixel_count == 0 || spp == 0) return RTP_OK;  // (no samples: the state stays as it is)
-  double ms = 0;
-  rs = launch(c, cam, nx, ny, spp, depth, 0u, pixel_begin, pixel_count, d_pixel_ids, d_state->rgba, d_state->seed,
-              d_state->live_bounces, (hipStream_t)hip_stream, stats ? &ms : nullptr, nullptr, nullptr, 0, nullptr, true,
-              d_state->m2);
-  if (rs == RTP_OK && stats) {
-    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RenderJob j = resume_job(cam, nx, ny, spp, depth, *d_state);
+  j.pixel_begin = pixel_begin, j.npix = pixel_count, j.d_ids = d_pixel_ids;
+  return launch_device(c, j, nullptr, hip_stream, stats);
 }
 
 // Host arrays, synchronous: the state is uploaded, resumed and copied back.
 rtp_status rtp_render_resume(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                              int32_t depth, const int64_t* pixel_ids, int64_t pixel_count,
                              const rtp_render_state* host_state, rtp_stats* stats) {
-  rtp_status rs = check_resume_args(c, cam, nx, ny, spp, depth, host_state, "rtp_render_resume");
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_resume_args(c, cam, nx, ny, spp, depth, host_state, "rtp_render_resume"));
   const int64_t npx = (int64_t)nx * ny;
   if (pixel_count < 0 || (!pixel_ids && pixel_count != npx))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_resume: without a pixel list pixel_count must be nx * ny");
@@ -1383,46 +1375,27 @@ rtp_status rtp_render_resume(rtp_context* c, const rtp_camera* cam, int32_t nx, 
   if (pixel_count == 0 || spp == 0) return RTP_OK;
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)pixel_count;
+  const rtp_render_state& hs = *host_state;
+  DevBufs b;
   int64_t* d_ids = nullptr;
   rtp_render_state d{};
-  auto cleanup = [&]() {
-    if (d_ids) (void)hipFree(d_ids);
-    if (d.rgba) (void)hipFree(d.rgba);
-    if (d.seed) (void)hipFree(d.seed);
-    if (d.live_bounces) (void)hipFree(d.live_bounces);
-    if (d.m2) (void)hipFree(d.m2);
-  };
-  auto up = [&](auto** dst, const auto* src, size_t bytes) {
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(dst), bytes);
-    if (e == hipSuccess) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  };
-  hipError_t e = up(&d.rgba, host_state->rgba, n * 16);
-  if (e == hipSuccess) e = up(&d.seed, host_state->seed, n * 4);
-  if (e == hipSuccess && host_state->live_bounces) e = up(&d.live_bounces, host_state->live_bounces, n * 4);
-  if (e == hipSuccess && host_state->m2) e = up(&d.m2, host_state->m2, n * 4);
-  if (e == hipSuccess && pixel_ids) e = up(&d_ids, pixel_ids, n * 8);
-  if (e != hipSuccess) {
-    cleanup();
-    return hip_fail(e, "render_resume: device buffers");
-  }
+  HIP_TRY_AS("render_resume: device buffers", b.get(&d.rgba, n * 16, (const float*)hs.rgba));
+  HIP_TRY_AS("render_resume: device buffers", b.get(&d.seed, n * 4, (const uint32_t*)hs.seed));
+  if (hs.live_bounces)
+    HIP_TRY_AS("render_resume: device buffers", b.get(&d.live_bounces, n * 4, (const uint32_t*)hs.live_bounces));
+  if (hs.m2) HIP_TRY_AS("render_resume: device buffers", b.get(&d.m2, n * 4, (const float*)hs.m2));
+  if (pixel_ids) HIP_TRY_AS("render_resume: device buffers", b.get(&d_ids, n * 8, pixel_ids));
   double ms = 0;
-  rs = launch(c, cam, nx, ny, spp, depth, 0u, 0, pixel_count, d_ids, d.rgba, d.seed, d.live_bounces, nullptr, &ms,
-              nullptr, nullptr, 0, nullptr, true, d.m2);
-  if (rs == RTP_OK) {
-    e = hipMemcpy(host_state->rgba, d.rgba, n * 16, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(host_state->seed, d.seed, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d.live_bounces)
-      e = hipMemcpy(host_state->live_bounces, d.live_bounces, n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && d.m2) e = hipMemcpy(host_state->m2, d.m2, n * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rs = hip_fail(e, "render_resume: copy back");
-  }
-  cleanup();
-  if (rs == RTP_OK && stats) {
-    stats->samples = (uint64_t)pixel_count * (uint64_t)spp;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RenderJob j = resume_job(cam, nx, ny, spp, depth, d);
+  j.npix = pixel_count, j.d_ids = d_ids;
+  j.kernel_ms = &ms;
+  RTP_TRY(launch(c, j));
+  HIP_TRY_AS("render_resume: copy back", DevBufs::back(hs.rgba, d.rgba, n * 16));
+  HIP_TRY_AS("render_resume: copy back", DevBufs::back(hs.seed, d.seed, n * 4));
+  HIP_TRY_AS("render_resume: copy back", DevBufs::back(hs.live_bounces, d.live_bounces, n * 4));
+  HIP_TRY_AS("render_resume: copy back", DevBufs::back(hs.m2, d.m2, n * 4));
+  fill_stats(stats, (uint64_t)pixel_count * (uint64_t)spp, ms);
+  return RTP_OK;
 }
 
 }  // extern "C"
@@ -1443,8 +1416,7 @@ rtp_status acquire_view_table(rtp_context* c, int32_t n, size_t* slot) {
   for (size_t i = 0; i < c->view_tables.size() && pick == c->view_tables.size(); i++)
     if (usable(c->view_tables[i])) pick = i;  // (too small: reallocated below)
   if (pick == c->view_tables.size() && c->view_tables.size() >= 16) {
-    rtp_status rs = drain(c);
-    if (rs != RTP_OK) return rs;
+    RTP_TRY(drain(c));
     for (rtp_context::ViewTable& t : c->view_tables) t.in_flight = false;
     pick = 0;
     for (size_t i = 1; i < c->view_tables.size(); i++)
@@ -1469,11 +1441,8 @@ rtp_status acquire_view_table(rtp_context* c, int32_t n, size_t* slot) {
 // the batched launch unless the scene or the environment asks for the
 // per-view loop (include/rtp.h rtp_render_views_device)
 bool views_batched(const rtp_context* c) {
-  auto is = [](const char* name, char v) {
-    const char* e = getenv(name);
-    return e && e[0] == v;
-  };
-  return !c->use_bvh && !is("RTP_KERNEL", '1') && !is("RTP_DEBUG_STATS", '1') && !is("RTP_VIEWS_BATCH", '0');
+  return !c->use_bvh && !env_is("RTP_KERNEL", '1') && !env_is("RTP_DEBUG_STATS", '1') &&
+         !env_is("RTP_VIEWS_BATCH", '0');
 }
 
 rtp_status check_views_args(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
@@ -1481,8 +1450,7 @@ rtp_status check_views_args(rtp_context* c, const rtp_view* views, int32_t n_vie
   if (!c || !views) return fail(RTP_ERR_INVALID_ARGUMENT, "render_views: NULL argument");
   if (n_views < 1) return fail(RTP_ERR_INVALID_ARGUMENT, "render_views: n_views must be >= 1");
   for (int32_t v = 0; v < n_views; v++) {
-    rtp_status rs = check_render_args(c, &views[v].camera, nx, ny, spp, depth);
-    if (rs != RTP_OK) return rs;
+    RTP_TRY(check_render_args(c, &views[v].camera, nx, ny, spp, depth));
   }
   // (entries are 32-bit in the kernel)
   if ((int64_t)n_views * nx * ny > INT32_MAX)
@@ -1499,10 +1467,12 @@ rtp_status render_views_device(rtp_context* c, const rtp_view* views, int32_t n_
     double total = 0;
     for (int32_t v = 0; v < n_views; v++) {
       double ms = 0;
-      rtp_status rs = launch(c, &views[v].camera, nx, ny, spp, depth, views[v].seed_base, 0, N, nullptr,
-                             d_out + 4 * N * v, d_seed ? d_seed + N * v : nullptr, d_live ? d_live + N * v : nullptr,
-                             stream, kernel_ms ? &ms : nullptr);
-      if (rs != RTP_OK) return rs;
+      RenderJob j = job_of(&views[v].camera, nx, ny, spp, depth, views[v].seed_base);
+      j.npix = N;
+      j.d_out = d_out + 4 * N * v;
+      j.d_seed = d_seed ? d_seed + N * v : nullptr, j.d_live = d_live ? d_live + N * v : nullptr;
+      j.stream = stream, j.kernel_ms = kernel_ms ? &ms : nullptr;
+      RTP_TRY(launch(c, j));
       total += ms;
     }
     if (kernel_ms) *kernel_ms = total;
@@ -1510,8 +1480,7 @@ rtp_status render_views_device(rtp_context* c, const rtp_view* views, int32_t n_
   }
   HIP_TRY(hipSetDevice(c->device));
   size_t slot = 0;
-  rtp_status rs = acquire_view_table(c, n_views, &slot);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(acquire_view_table(c, n_views, &slot));
   rtp::DevView* const host = c->view_tables[slot].host;
   rtp::DevView* const dev = c->view_tables[slot].dev;
   for (int32_t v = 0; v < n_views; v++) {
@@ -1521,8 +1490,11 @@ rtp_status render_views_device(rtp_context* c, const rtp_view* views, int32_t n_
   }
   HIP_TRY(hipMemcpyAsync(dev, host, (size_t)n_views * sizeof(rtp::DevView), hipMemcpyHostToDevice, stream));
   c->view_tables[slot].in_flight = true;  // (from the upload on: the event below closes the slot's use)
-  rs = launch(c, nullptr, nx, ny, spp, depth, 0u, 0, N * n_views, nullptr, d_out, d_seed, d_live, stream, kernel_ms,
-              nullptr, nullptr, 0, dev);
+  RenderJob j = job_of(nullptr, nx, ny, spp, depth, 0u);  // (cameras and seed bases are in the table)
+  j.d_views = dev, j.npix = N * n_views;
+  j.d_out = d_out, j.d_seed = d_seed, j.d_live = d_live;
+  j.stream = stream, j.kernel_ms = kernel_ms;
+  const rtp_status rs = launch(c, j);
   HIP_TRY(hipEventRecord(c->view_tables[slot].used, stream));
   return rs;
 }
@@ -1536,53 +1508,33 @@ extern "C" {
 rtp_status rtp_render_views_device(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
                                    int32_t spp, int32_t depth, float* d_rgba_out, const rtp_pixel_aux* aux,
                                    void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_views_args(c, views, n_views, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_views_args(c, views, n_views, nx, ny, spp, depth));
   if (!d_rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_views_device: bad output");
   double ms = 0;
-  rs = render_views_device(c, views, n_views, nx, ny, spp, depth, d_rgba_out, aux ? aux->final_seed : nullptr,
-                           aux ? aux->live_bounces : nullptr, (hipStream_t)hip_stream, stats ? &ms : nullptr);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = (uint64_t)n_views * (uint64_t)nx * (uint64_t)ny * (uint64_t)spp;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RTP_TRY(render_views_device(c, views, n_views, nx, ny, spp, depth, d_rgba_out, aux ? aux->final_seed : nullptr,
+                              aux ? aux->live_bounces : nullptr, (hipStream_t)hip_stream, stats ? &ms : nullptr));
+  fill_stats(stats, (uint64_t)n_views * (uint64_t)nx * (uint64_t)ny * (uint64_t)spp, ms);
+  return RTP_OK;
 }
 
 rtp_status rtp_render_views(rtp_context* c, const rtp_view* views, int32_t n_views, int32_t nx, int32_t ny,
                             int32_t spp, int32_t depth, float* rgba_out, rtp_stats* stats) {
-  rtp_status rs = check_views_args(c, views, n_views, nx, ny, spp, depth);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_views_args(c, views, n_views, nx, ny, spp, depth));
   if (!rgba_out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_views: rgba_out is NULL");
   HIP_TRY(hipSetDevice(c->device));
   const int64_t n = (int64_t)n_views * nx * ny;
+  DevBufs b;
   float* d_out = nullptr;
   uint32_t* d_live = nullptr;
-  hipError_t e = hipMalloc(&d_out, (size_t)n * 16);
-  if (e == hipSuccess) e = hipMalloc(&d_live, (size_t)n * 4);
+  HIP_TRY_AS("render_views: device buffers", b.get(&d_out, (size_t)n * 16));
+  HIP_TRY_AS("render_views: device buffers", b.get(&d_live, (size_t)n * 4));
   std::vector<uint32_t> live((size_t)n);
   double ms = 0;
-  if (e != hipSuccess) rs = hip_fail(e, "render_views: device buffers");
-  if (rs == RTP_OK) rs = render_views_device(c, views, n_views, nx, ny, spp, depth, d_out, nullptr, d_live, nullptr, &ms);
-  if (rs == RTP_OK) {
-    e = hipMemcpy(rgba_out, d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(live.data(), d_live, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rs = hip_fail(e, "render_views: copy back");
-  }
-  if (d_out) (void)hipFree(d_out);
-  if (d_live) (void)hipFree(d_live);
-  if (rs != RTP_OK) return rs;
-  if (stats) {
-    *stats = rtp_stats{};
-    stats->samples = (uint64_t)n * (uint64_t)spp;
-    for (int64_t i = 0; i < n; i++) {
-      stats->live_bounces += live[i];
-      const float* px = rgba_out + 4 * i;
-      stats->nan_pixels += (std::isnan(px[0]) || std::isnan(px[1]) || std::isnan(px[2])) ? 1 : 0;
-    }
-    stats->kernel_ms = ms;
-  }
+  RTP_TRY(render_views_device(c, views, n_views, nx, ny, spp, depth, d_out, nullptr, d_live, nullptr, &ms));
+  HIP_TRY_AS("render_views: copy back", DevBufs::back(rgba_out, d_out, (size_t)n * 16));
+  HIP_TRY_AS("render_views: copy back", DevBufs::back(live.data(), d_live, (size_t)n * 4));
+  fill_stats(stats, (uint64_t)n * (uint64_t)spp, ms);
+  sum_stats(stats, rgba_out, live.data(), n);
   return RTP_OK;
 }
 
@@ -1595,22 +1547,14 @@ rtp_status launch_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, int3
   camera_setup(cam, nx, ny, &p.cam);
   p.nx = nx, p.ny = ny, p.npix = (int64_t)nx * ny;
   p.g0 = g0, p.g1 = g1, p.prim = prim;
-  if (kernel_ms) HIP_TRY(hipEventRecord(c->ev0, stream));
-  HIP_TRY(rtp_launch_guides(c->d_scene, &p, c->use_bvh ? 1 : 0, stream));
-  HIP_TRY(hipEventRecord(c->done, stream));  // (rtp_set_scene waits for it before it frees the scene)
-  c->pending = true;
-  if (kernel_ms) {
-    HIP_TRY(hipEventRecord(c->ev1, stream));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    *kernel_ms = ms;
-  }
-  return RTP_OK;
+  // (done is recorded: rtp_set_scene waits for it before it frees the scene)
+  return timed_launch(c, stream, kernel_ms, true, [&]() -> rtp_status {
+    HIP_TRY(rtp_launch_guides(c->d_scene, &p, c->use_bvh ? 1 : 0, stream));
+    return RTP_OK;
+  });
 }
 rtp_status check_guides_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, bool any_output) {
-  rtp_status rs = check_render_args(c, cam, nx, ny, 0, 1);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_render_args(c, cam, nx, ny, 0, 1));
   if (!any_output) return fail(RTP_ERR_INVALID_ARGUMENT, "render_guides: every output is NULL");
   return RTP_OK;
 }
@@ -1618,47 +1562,31 @@ rtp_status check_guides_args(rtp_context* c, const rtp_camera* cam, int32_t nx, 
 
 rtp_status rtp_render_guides_device(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, float* d_g0,
                                     float* d_g1, int32_t* d_prim, void* hip_stream, rtp_stats* stats) {
-  rtp_status rs = check_guides_args(c, cam, nx, ny, d_g0 || d_g1 || d_prim);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_guides_args(c, cam, nx, ny, d_g0 || d_g1 || d_prim));
   double ms = 0;
-  rs = launch_guides(c, cam, nx, ny, d_g0, d_g1, d_prim, (hipStream_t)hip_stream, stats ? &ms : nullptr);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = (uint64_t)nx * ny;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RTP_TRY(launch_guides(c, cam, nx, ny, d_g0, d_g1, d_prim, (hipStream_t)hip_stream, stats ? &ms : nullptr));
+  fill_stats(stats, (uint64_t)nx * ny, ms);
+  return RTP_OK;
 }
 
 rtp_status rtp_render_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, float* g0, float* g1,
                              int32_t* prim, rtp_stats* stats) {
-  rtp_status rs = check_guides_args(c, cam, nx, ny, g0 || g1 || prim);
-  if (rs != RTP_OK) return rs;
+  RTP_TRY(check_guides_args(c, cam, nx, ny, g0 || g1 || prim));
   HIP_TRY(hipSetDevice(c->device));
   const size_t n = (size_t)nx * ny;
-  void* d[3] = {nullptr, nullptr, nullptr};
-  void* h[3] = {g0, g1, prim};
-  const size_t sz[3] = {16 * n, 16 * n, 4 * n};
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 3 && e == hipSuccess; k++)
-    if (h[k]) e = hipMalloc(&d[k], sz[k]);
+  DevBufs b;
+  float *d_g0 = nullptr, *d_g1 = nullptr;
+  int32_t* d_prim = nullptr;
+  if (g0) HIP_TRY_AS("render_guides: device buffers", b.get(&d_g0, 16 * n));
+  if (g1) HIP_TRY_AS("render_guides: device buffers", b.get(&d_g1, 16 * n));
+  if (prim) HIP_TRY_AS("render_guides: device buffers", b.get(&d_prim, 4 * n));
   double ms = 0;
-  if (e == hipSuccess) {
-    rs = launch_guides(c, cam, nx, ny, (float*)d[0], (float*)d[1], (int32_t*)d[2], nullptr, &ms);
-    for (int k = 0; k < 3 && rs == RTP_OK; k++)
-      if (h[k] && (e = hipMemcpy(h[k], d[k], sz[k], hipMemcpyDeviceToHost)) != hipSuccess)
-        rs = hip_fail(e, "render_guides: copy back");
-  } else {
-    rs = hip_fail(e, "render_guides: device buffers");
-  }
-  for (void* p : d)
-    if (p) (void)hipFree(p);
-  if (rs == RTP_OK && stats) {
-    *stats = rtp_stats{};
-    stats->samples = n;
-    stats->kernel_ms = ms;
-  }
-  return rs;
+  RTP_TRY(launch_guides(c, cam, nx, ny, d_g0, d_g1, d_prim, nullptr, &ms));
+  HIP_TRY_AS("render_guides: copy back", DevBufs::back(g0, d_g0, 16 * n));
+  HIP_TRY_AS("render_guides: copy back", DevBufs::back(g1, d_g1, 16 * n));
+  HIP_TRY_AS("render_guides: copy back", DevBufs::back(prim, d_prim, 4 * n));
+  fill_stats(stats, n, ms);
+  return RTP_OK;
 }
 
 // Diagnostics: sums of the pool kernel's per-wave counters from the last launch
@@ -1697,15 +1625,13 @@ rtp_status rtp_eval_primitive(rtp_context* c, int32_t kind, const void* in, void
     if (!tab) return fail(RTP_ERR_DEVICE, "rtp_eval_primitive: RNG jump tables are not built (policy or memory)");
   }
   const int dk = kind <= 3 ? kind : (kind == 6 ? 5 : 4);  // device kinds: 4 gather, 5 one dead step
+  DevBufs b;
   void *din = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&din, (size_t)n * 4));
-  hipError_t e = hipMalloc(&dout, (size_t)n * 4);
-  if (e == hipSuccess) e = hipMemcpy(din, in, (size_t)n * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = rtp_launch_eval_primitive(dk, din, dout, n, tab, which_threshold(2), which_threshold(3), nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  if (e != hipSuccess) return hip_fail(e, "rtp_eval_primitive");
+  HIP_TRY_AS("rtp_eval_primitive", b.get(&din, (size_t)n * 4, in));
+  HIP_TRY_AS("rtp_eval_primitive", b.get(&dout, (size_t)n * 4));
+  HIP_TRY_AS("rtp_eval_primitive",
+             rtp_launch_eval_primitive(dk, din, dout, n, tab, which_threshold(2), which_threshold(3), nullptr));
+  HIP_TRY_AS("rtp_eval_primitive", DevBufs::back(out, dout, (size_t)n * 4));
   return RTP_OK;
 }
 
@@ -1713,20 +1639,18 @@ rtp_status rtp_eval_primitive(rtp_context* c, int32_t kind, const void* in, void
 // prefilter (rtp_eval_closest_kernel; 7 u32 per ray).
 rtp_status rtp_debug_closest_hit(rtp_context* c, const float* rays, int64_t n, uint32_t* out) {
   if (!c || !rays || !out || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_closest_hit: bad arguments");
-  if (!c->d_scene) return fail(RTP_ERR_NO_SCENE, "rtp_debug_closest_hit: no scene set");
+  // (has_scene, not d_scene: the device scene exists from rtp_create on, and
+  // names freed arrays after an rtp_set_scene whose upload failed)
+  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "rtp_debug_closest_hit: no scene set");
   if (n == 0) return RTP_OK;
   HIP_TRY(hipSetDevice(c->device));
-  void *din = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc(&din, (size_t)n * 24));
-  hipError_t e = hipMalloc(&dout, (size_t)n * 28);
-  if (e == hipSuccess) e = hipMemcpy(din, rays, (size_t)n * 24, hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = rtp_launch_eval_closest(c->d_scene, static_cast<const float*>(din), static_cast<uint32_t*>(dout), n,
-                                c->use_bvh ? 1 : 0, nullptr);
-  if (e == hipSuccess) e = hipMemcpy(out, dout, (size_t)n * 28, hipMemcpyDeviceToHost);
-  (void)hipFree(din);
-  if (dout) (void)hipFree(dout);
-  if (e != hipSuccess) return hip_fail(e, "rtp_debug_closest_hit");
+  DevBufs b;
+  float* din = nullptr;
+  uint32_t* dout = nullptr;
+  HIP_TRY_AS("rtp_debug_closest_hit", b.get(&din, (size_t)n * 24, rays));
+  HIP_TRY_AS("rtp_debug_closest_hit", b.get(&dout, (size_t)n * 28));
+  HIP_TRY_AS("rtp_debug_closest_hit", rtp_launch_eval_closest(c->d_scene, din, dout, n, c->use_bvh ? 1 : 0, nullptr));
+  HIP_TRY_AS("rtp_debug_closest_hit", DevBufs::back(out, dout, (size_t)n * 28));
   return RTP_OK;
 }
 

@@ -1,0 +1,90 @@
+"""Digest of the device code in a librtp.so (development tool): for every
+gfx950 code object of the library's fat binary, the SHA-256 of its .text (the
+kernels' instructions) and of its .rodata (the kernel descriptors: register
+and LDS budgets).  Two builds whose listings agree run the same kernels, so a
+host-only change can be checked without a GPU:
+
+    python tools/device_code_digest.py [path/to/librtp.so ...]
+
+Only these two sections are hashed: the fat binary as a whole also carries
+build-identifier bytes that differ between two builds of the same sources.
+The tool hashes bytes; it does not disassemble or search them.
+"""
+import hashlib
+import os
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEFAULT_LIB = os.path.join(ROOT, "raytracingtherestofyourlife_amd", "librtp.so")
+MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+ARCH = "gfx950"
+
+
+def objcopy() -> str:
+    for cand in (os.environ.get("LLVM_OBJCOPY"), "/opt/rocm/lib/llvm/bin/llvm-objcopy", "/opt/rocm/llvm/bin/llvm-objcopy",
+                 shutil.which("llvm-objcopy")):
+        if cand and os.path.exists(cand):
+            return cand
+    raise RuntimeError("llvm-objcopy not found")
+
+
+def fatbin(lib: str) -> bytes:
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "fatbin")
+        subprocess.run([objcopy(), "--dump-section", f".hip_fatbin={out}", lib, os.path.join(tmp, "copy")], check=True)
+        with open(out, "rb") as f:
+            return f.read()
+
+
+def code_objects(blob: bytes):
+    """(bundle index, entry id, bytes) of every ARCH entry of every bundle
+    (one bundle per translation unit with kernels, in link order)."""
+    pos, bundle = blob.find(MAGIC), 0
+    while pos >= 0:
+        (n,) = struct.unpack_from("<Q", blob, pos + len(MAGIC))
+        at = pos + len(MAGIC) + 8
+        for _ in range(n):
+            off, size, idlen = struct.unpack_from("<QQQ", blob, at)
+            ident = blob[at + 24:at + 24 + idlen].decode()
+            at += 24 + idlen
+            if ARCH in ident:
+                yield bundle, ident, blob[pos + off:pos + off + size]
+        pos, bundle = blob.find(MAGIC, pos + len(MAGIC)), bundle + 1
+
+
+def elf_sections(elf: bytes) -> dict:
+    """name -> bytes of an ELF64 little-endian object's sections"""
+    if elf[:4] != b"\x7fELF" or elf[4] != 2 or elf[5] != 1:
+        raise RuntimeError("not an ELF64 little-endian code object")
+    (shoff,) = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
+    heads = []
+    for i in range(shnum):
+        name, kind, _flags, _addr, off, size = struct.unpack_from("<IIQQQQ", elf, shoff + i * shentsize)
+        heads.append((name, kind, off, size))
+    _, _, stroff, strsize = heads[shstrndx]
+    names = elf[stroff:stroff + strsize]
+    out = {}
+    for name, kind, off, size in heads:
+        label = names[name:names.index(b"\0", name)].decode()
+        out[label] = b"" if kind == 8 else elf[off:off + size]  # (8: SHT_NOBITS)
+    return out
+
+
+def digest(lib: str):
+    rows = []
+    for bundle, ident, elf in code_objects(fatbin(lib)):
+        sec = elf_sections(elf)
+        rows.append((bundle, ident, *(hashlib.sha256(sec.get(s, b"")).hexdigest() for s in (".text", ".rodata"))))
+    return rows
+
+
+if __name__ == "__main__":
+    for lib in sys.argv[1:] or [DEFAULT_LIB]:
+        print(lib)
+        for bundle, ident, text, rodata in digest(lib):
+            print(f"  [{bundle}] {ident}\n      .text   {text}\n      .rodata {rodata}")

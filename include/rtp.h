@@ -490,6 +490,15 @@ int32_t rtp_debug_counters(rtp_context* ctx, uint64_t* out, int32_t n_out);
  * bits, kind, index), 1 if the ray fell back to the exact scan. */
 rtp_status rtp_debug_closest_hit(rtp_context* ctx, const float* rays, int64_t n, uint32_t* out);
 
+/* Diagnostics: one depth of the path kernel's bounce (intersect, collect,
+ * material, generate, pdfs, scatter) for n rays (o, d: 6 floats each) with
+ * their RNG states, as depth 0 of a two-deep path.  out (host, 15 u32 per
+ * ray): 0 the path goes on / 1 it missed / 2 it ended on a light; emitted
+ * (0 unless 2); attenuation[0] (1 unless 0); the next origin and direction
+ * (the ray's own unless 0); the RNG state after the depth's draws; 1 if the
+ * attenuation is not finite. */
+rtp_status rtp_debug_bounce(rtp_context* ctx, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out);
+
 /* Diagnostics: how the current scene's spheres are searched by a render
  * (rtp_render*, without RTP_DEBUG_STATS or a wave plan): 0 every sphere in
  * order (fewer than 9 spheres), 1 the threaded sphere BVH in global memory,

@@ -182,6 +182,58 @@ def randf_stream(seed: int, n: int):
     return vals, int(s.value)
 
 
+# ------------------------------------------- stage exports (rtp_oracle.h) ---
+# name: (entry point, it takes the scene, words per case, words per result)
+STAGE_FNS = {
+    "rng": ("rtpo_stage_rng", False, 1, 3),
+    "which": ("rtpo_stage_which", False, 1, 2),
+    "onb": ("rtpo_stage_onb", False, 6, 12),
+    "quad_hit": ("rtpo_stage_quad_hit", False, 20, 12),
+    "sphere_hit": ("rtpo_stage_sphere_hit", False, 12, 8),
+    "material": ("rtpo_stage_material", True, 20, 14),
+    "dielectric_scatter": ("rtpo_stage_dielectric_scatter", False, 12, 9),
+    "generator": ("rtpo_stage_generator", True, 9, 4),
+    "light_pdf": ("rtpo_stage_light_pdf", True, 10, 2),
+    "scatter": ("rtpo_stage_scatter", True, 26, 10),
+    "collect": ("rtpo_stage_collect", True, 1, 7),
+}
+BOUNCE_PASSES, BOUNCE_WORDS = 13, 37
+
+
+def _stage_fns():
+    L = lib()
+    if not hasattr(L, "_stages_ready"):
+        u32p, scp = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Scene)
+        for fn, takes_scene, _, _ in STAGE_FNS.values():
+            getattr(L, fn).argtypes = ([scp] if takes_scene else []) + [u32p, ctypes.c_int64, u32p]
+            getattr(L, fn).restype = None
+        L.rtpo_bounce.argtypes = [scp, ctypes.POINTER(ctypes.c_float), u32p, ctypes.c_int64, u32p]
+        L.rtpo_bounce.restype = None
+        L._stages_ready = True
+    return L
+
+
+def stage(name: str, scene: Scene, cases) -> np.ndarray:
+    """One rtpo_stage_* over rows of 32-bit words: (n, kin) -> (n, kout) uint32."""
+    fn, takes_scene, kin, kout = STAGE_FNS[name]
+    cases = np.ascontiguousarray(cases, dtype=np.uint32)
+    assert cases.ndim == 2 and cases.shape[1] == kin, (name, cases.shape)
+    out = np.zeros((len(cases), kout), dtype=np.uint32)
+    args = ([ctypes.byref(scene)] if takes_scene else []) + [_up(cases), len(cases), _up(out)]
+    getattr(_stage_fns(), fn)(*args)
+    return out
+
+
+def bounce(scene: Scene, rays, seeds) -> np.ndarray:
+    """rtpo_bounce: (n, 13, 37) uint32, every ray's state after every pass of one depth."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint32)
+    assert len(seeds) == len(rays)
+    out = np.zeros((len(rays), BOUNCE_PASSES, BOUNCE_WORDS), dtype=np.uint32)
+    _stage_fns().rtpo_bounce(ctypes.byref(scene), _fp(rays), _up(seeds), len(rays), _up(out))
+    return out
+
+
 # ------------------------------------------------------------ -direct mode ---
 class DirectCam(ctypes.Structure):
     """Mirror of rtpo_direct_cam."""

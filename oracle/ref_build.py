@@ -16,6 +16,12 @@ receives the built tree).
   oracle/_ref/scene_unchanged_check   tests/cpp/scene_unchanged_check.cpp +
                                       CornellBox.cpp (the reference's scene
                                       against rtp_cornell_box)
+  oracle/_ref/ref_stages              tests/cpp/ref_stage_driver.cpp over the
+                                      reference's header-only worklets
+                                      (pathtracing/*.h, included by name and
+                                      found with -iquote), whose VTK-m names
+                                      resolve in tests/cpp/vtkm_min/; it needs
+                                      neither librtp.so nor include/vtkm_compat
 
 raytracingtherestofyourlife_amd/build.py build_main_unchanged() calls
 build_ref(); `python oracle/ref_build.py [--force]` does the same by hand.
@@ -32,6 +38,31 @@ REFERENCE_SOURCES = ("main.cc", "CornellBox.cpp")
 MAIN_UNCHANGED = os.path.join(REF_OUT, "main_cc")
 SCENE_CHECK = os.path.join(REF_OUT, "scene_unchanged_check")
 SCENE_CHECK_SRC = os.path.join(ROOT, "tests", "cpp", "scene_unchanged_check.cpp")
+REF_STAGES = os.path.join(REF_OUT, "ref_stages")
+REF_STAGES_SRC = os.path.join(ROOT, "tests", "cpp", "ref_stage_driver.cpp")
+VTKM_MIN = os.path.join(ROOT, "tests", "cpp", "vtkm_min")
+# the reference headers the stage driver includes, directly or through one another
+REF_STAGE_HEADERS = tuple(os.path.join("pathtracing", h) for h in (
+    "PdfWorklet.h", "EmitWorklet.h", "ScatterWorklet.h", "SurfaceWorklets.h", "Surface.h", "AABBSurface.h", "onb.h",
+    "wangXor.h", "vec3.h", "Record.h"))
+
+
+def build_ref_stages(reference_dir: str, force: bool = False):
+    """Build REF_STAGES where the reference's worklet headers exist; None otherwise.  The flags
+    are the oracle's: -O2, no FMA contraction, no fast-math (x86-64 SSE2 arithmetic)."""
+    deps = [os.path.join(reference_dir, h) for h in REF_STAGE_HEADERS]
+    if not all(os.path.exists(d) for d in deps):
+        return None
+    deps += [REF_STAGES_SRC, os.path.join(VTKM_MIN, "vtkm_min.h")]
+    os.makedirs(REF_OUT, exist_ok=True)
+    if force or _newer(deps, REF_STAGES):
+        res = subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
+                              "-I", VTKM_MIN, "-iquote", reference_dir, REF_STAGES_SRC, "-o", REF_STAGES + ".tmp"],
+                             capture_output=True, text=True)
+        if res.returncode != 0:
+            raise RuntimeError(f"g++ failed on the stage driver:\n{res.stderr[-4000:]}")
+        os.replace(REF_STAGES + ".tmp", REF_STAGES)
+    return REF_STAGES
 
 
 def _newer(deps, target) -> bool:
@@ -39,9 +70,10 @@ def _newer(deps, target) -> bool:
 
 
 def build_ref(reference_dir: str, lib: str, force: bool = False):
-    """Build MAIN_UNCHANGED and SCENE_CHECK from the reference tree at
+    """Build REF_STAGES, MAIN_UNCHANGED and SCENE_CHECK from the reference tree at
     reference_dir against the built library `lib` (librtp.so; rpath relative
     to oracle/_ref/); None when the reference is absent."""
+    build_ref_stages(reference_dir, force=force)
     if not all(os.path.exists(os.path.join(reference_dir, f)) for f in REFERENCE_SOURCES):
         return None
     libdir = os.path.dirname(os.path.abspath(lib))

@@ -856,6 +856,283 @@ typedef struct {
 #define FOR_RAYS for (int64_t i = 0; i < n; i++)
 #define OMP_FOR _Pragma("omp parallel for schedule(static) num_threads(nthreads)")
 
+/* the buffers of one render: n rays, depth slices of A and E */
+static void soa_alloc(soa_t* R, int64_t n, int32_t depth) {
+  float** fl[] = {&R->ox, &R->oy, &R->oz, &R->dx, &R->dy, &R->dz, &R->ht, &R->hnx, &R->hny, &R->hnz, &R->hpx,
+                  &R->hpy, &R->hpz, &R->sox, &R->soy, &R->soz, &R->sdx, &R->sdy, &R->sdz, &R->sax, &R->say, &R->saz,
+                  &R->gx, &R->gy, &R->gz, &R->sum, &R->tmin, &R->tx, &R->ty, &R->tz};
+  for (size_t k = 0; k < sizeof(fl) / sizeof(fl[0]); k++) *fl[k] = (float*)calloc(n, sizeof(float));
+  float** dl[] = {&R->Ax, &R->Ay, &R->Az, &R->Ex, &R->Ey, &R->Ez};
+  for (size_t k = 0; k < 6; k++) *dl[k] = (float*)calloc(n * depth, sizeof(float));
+  R->status = (uint8_t*)calloc(n, 1);
+  R->hm = (int32_t*)calloc(n, 4);
+  R->htx = (int32_t*)calloc(n, 4);
+  R->which = (int32_t*)calloc(n, 4);
+  R->seeds = (uint32_t*)calloc(n, 4);
+  R->live = (uint32_t*)calloc(n, 4);
+}
+static void soa_free(soa_t* R) {
+  float* fl[] = {R->ox, R->oy, R->oz, R->dx, R->dy, R->dz, R->ht, R->hnx, R->hny, R->hnz, R->hpx, R->hpy,
+                 R->hpz, R->sox, R->soy, R->soz, R->sdx, R->sdy, R->sdz, R->sax, R->say, R->saz, R->gx, R->gy,
+                 R->gz, R->sum, R->tmin, R->tx, R->ty, R->tz, R->Ax, R->Ay, R->Az, R->Ex, R->Ey, R->Ez};
+  for (size_t k = 0; k < sizeof(fl) / sizeof(fl[0]); k++) free(fl[k]);
+  free(R->status), free(R->hm), free(R->htx), free(R->which), free(R->seeds), free(R->live);
+}
+
+/* rtpo_bounce's record of every ray after pass c of depth dep (rtp_oracle.h: RTPO_BOUNCE_*) */
+static inline uint32_t fbits(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return u;
+}
+static void soa_record(const soa_t* R, int64_t n, int dep, int c, uint32_t* rec) {
+  if (!rec) return;
+  const int64_t off = (int64_t)dep * n;
+  for (int64_t i = 0; i < n; i++) {
+    uint32_t* w = rec + ((int64_t)i * RTPO_BOUNCE_PASSES + c) * RTPO_BOUNCE_WORDS;
+    const float f[] = {R->ht[i],  R->hnx[i], R->hny[i], R->hnz[i], R->hpx[i], R->hpy[i], R->hpz[i]};
+    const float g[] = {R->sox[i], R->soy[i], R->soz[i], R->sdx[i], R->sdy[i], R->sdz[i], R->sax[i], R->say[i], R->saz[i]};
+    const float h[] = {R->gx[i], R->gy[i], R->gz[i], R->sum[i], R->Ex[off + i], R->Ey[off + i], R->Ez[off + i],
+                       R->Ax[off + i], R->Ay[off + i], R->Az[off + i], R->ox[i], R->oy[i], R->oz[i],
+                       R->dx[i], R->dy[i], R->dz[i]};
+    int k = 0;
+    w[k++] = R->status[i];
+    for (int j = 0; j < 7; j++) w[k++] = fbits(f[j]);
+    w[k++] = (uint32_t)R->hm[i];
+    w[k++] = (uint32_t)R->htx[i];
+    for (int j = 0; j < 9; j++) w[k++] = fbits(g[j]);
+    w[k++] = (uint32_t)R->which[i];
+    for (int j = 0; j < 16; j++) w[k++] = fbits(h[j]);
+    w[k++] = R->seeds[i];
+  }
+}
+
+/* One depth of RenderCellsImpl (MapperPathTracer.cxx:286-301) over all n rays: the resets and thirteen
+ * passes, of which the stage exports run one at a time (passes: bit k is pass k). */
+#define RTPO_PASS_RESET (1u << 13) /* the per-depth resets, MapperPathTracer.cxx:287, 419-420 */
+#define RTPO_PASS_ALL 0x3fffu
+static void soa_depth(const rtpo_scene* sc, const lights* Lp, const soa_t* Rp, int64_t n, int dep, int32_t nthreads,
+                      uint32_t passes, uint32_t* rec) {
+  const soa_t R = *Rp;
+  const lights L = *Lp;
+  const float weight = (float)(1.0 / (float)2);
+  const float tmin_c = (float)0.001;
+  float* Ax = R.Ax + (int64_t)dep * n;
+  float* Ay = R.Ay + (int64_t)dep * n;
+  float* Az = R.Az + (int64_t)dep * n;
+  float* Ex = R.Ex + (int64_t)dep * n;
+  float* Ey = R.Ey + (int64_t)dep * n;
+  float* Ez = R.Ez + (int64_t)dep * n;
+  (void)nthreads;
+  if (passes & RTPO_PASS_RESET) {
+    OMP_FOR FOR_RAYS { R.sum[i] = 0; R.ht[i] = FLT_MAX; R.tmin[i] = tmin_c; }
+  }
+  if (passes & (1u << 0)) {
+    /* quad traversal (BVHTraverser over QuadLeafIntersector) */
+    OMP_FOR FOR_RAYS {
+      if (R.status[i] & 8) R.live[i]++;
+      if (!(R.status[i] & 8)) continue;
+      v3 o = mk(R.ox[i], R.oy[i], R.oz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
+      float closest = R.ht[i];
+      int hit = 0;
+      for (int q = 0; q < sc->n_quads; q++) {
+        const int32_t* id = sc->quad_ids[q];
+        hitrec tmp;
+        if (quad_intersect(o, d, R.tmin[i], closest, ld(sc->points[id[1]]), ld(sc->points[id[2]]),
+                           ld(sc->points[id[3]]), ld(sc->points[id[4]]), &tmp)) {
+          R.ht[i] = tmp.t;
+          R.hnx[i] = tmp.n.x, R.hny[i] = tmp.n.y, R.hnz[i] = tmp.n.z;
+          R.hpx[i] = tmp.p.x, R.hpy[i] = tmp.p.y, R.hpz[i] = tmp.p.z;
+          R.hm[i] = sc->quad_mat[q];
+          R.htx[i] = sc->quad_tex[q];
+          closest = tmp.t;
+          hit = 1;
+        }
+      }
+      R.status[i] |= (uint8_t)(hit << 2);
+      R.ht[i] = hit ? closest : FLT_MAX;
+    }
+  }
+  soa_record(&R, n, dep, 0, rec);
+  if (passes & (1u << 1)) {
+    /* sphere traversal */
+    OMP_FOR FOR_RAYS {
+      if (!(R.status[i] & 8)) continue;
+      v3 o = mk(R.ox[i], R.oy[i], R.oz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
+      float closest = R.ht[i];
+      int hit = 0;
+      for (int k = 0; k < sc->n_spheres; k++) {
+        hitrec tmp;
+        if (sphere_hit(o, d, R.tmin[i], closest, ld(sc->points[sc->sphere_point[k]]), sc->sphere_radius[k],
+                       &tmp)) {
+          closest = tmp.t;
+          R.hnx[i] = tmp.n.x, R.hny[i] = tmp.n.y, R.hnz[i] = tmp.n.z;
+          R.hpx[i] = tmp.p.x, R.hpy[i] = tmp.p.y, R.hpz[i] = tmp.p.z;
+          R.hm[i] = sc->sphere_mat[k];
+          R.htx[i] = sc->sphere_tex[k];
+          hit = 1;
+        }
+      }
+      R.status[i] |= (uint8_t)(hit << 2);
+      if ((R.status[i] & 8) && (R.status[i] & 4)) R.ht[i] = closest;
+    }
+  }
+  soa_record(&R, n, dep, 1, rec);
+  if (passes & (1u << 2)) {
+    /* CollectIntersecttWorklet */
+    OMP_FOR FOR_RAYS {
+      uint8_t st = R.status[i];
+      if (!((st & 8) && (st & 4))) {
+        st &= (uint8_t)~8u;
+        Ax[i] = 1.0f, Ay[i] = 1.0f, Az[i] = 1.0f;
+        Ex[i] = 0.0f, Ey[i] = 0.0f, Ez[i] = 0.0f;
+      }
+      st &= (uint8_t)~4u;
+      R.status[i] = st;
+    }
+  }
+  soa_record(&R, n, dep, 2, rec);
+  if (passes & (1u << 3)) {
+    /* LambertianWorklet */
+    OMP_FOR FOR_RAYS {
+      uint8_t st = R.status[i];
+      if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 0) {
+        const float* c = sc->tex[sc->tex_type[R.htx[i]]];
+        R.sax[i] = c[0], R.say[i] = c[1], R.saz[i] = c[2];
+        R.status[i] = (uint8_t)((st | 8u) & ~16u);
+        Ex[i] = 0, Ey[i] = 0, Ez[i] = 0;
+      }
+    }
+  }
+  soa_record(&R, n, dep, 3, rec);
+  if (passes & (1u << 4)) {
+    /* DiffuseLightWorklet */
+    OMP_FOR FOR_RAYS {
+      uint8_t st = R.status[i];
+      if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 1) {
+        const float* c = sc->tex[sc->tex_type[R.htx[i]]];
+        v3 nn = mk(R.hnx[i], R.hny[i], R.hnz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
+        int em = dot(nn, d) < 0.0;
+        Ex[i] = em ? c[0] : 0, Ey[i] = em ? c[1] : 0, Ez[i] = em ? c[2] : 0;
+        R.status[i] = 0; /* fin &= (false << 3) */
+      }
+    }
+  }
+  soa_record(&R, n, dep, 4, rec);
+  if (passes & (1u << 5)) {
+    /* DielectricWorklet */
+    OMP_FOR FOR_RAYS {
+      uint8_t st = R.status[i];
+      if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 2) {
+        float r = rtpo_randf(&R.seeds[i]);
+        v3 so, sd;
+        dielectric_scatter(mk(R.dx[i], R.dy[i], R.dz[i]), mk(R.hnx[i], R.hny[i], R.hnz[i]),
+                           mk(R.hpx[i], R.hpy[i], R.hpz[i]), sc->ior, r, &so, &sd);
+        R.sax[i] = 1, R.say[i] = 1, R.saz[i] = 1;
+        R.sox[i] = so.x, R.soy[i] = so.y, R.soz[i] = so.z;
+        R.sdx[i] = sd.x, R.sdy[i] = sd.y, R.sdz[i] = sd.z;
+        R.status[i] = (uint8_t)(st | 8u | 16u);
+        Ex[i] = 0, Ey[i] = 0, Ez[i] = 0;
+      }
+    }
+  }
+  soa_record(&R, n, dep, 5, rec);
+  if (passes & (1u << 6)) {
+    /* WhichGenerateDir (all rays) */
+    OMP_FOR FOR_RAYS R.which[i] = which_of(rtpo_randf(&R.seeds[i]));
+  }
+  soa_record(&R, n, dep, 6, rec);
+  if (passes & (1u << 7)) {
+    /* CosineGenerateDir */
+    OMP_FOR FOR_RAYS {
+      if (R.which[i] <= 1) {
+        v3 g = gen_cosine(mk(R.hnx[i], R.hny[i], R.hnz[i]), &R.seeds[i]);
+        R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
+      }
+    }
+  }
+  soa_record(&R, n, dep, 7, rec);
+  if (passes & (1u << 8)) {
+    /* QuadGenerateDir */
+    OMP_FOR FOR_RAYS {
+      if (R.which[i] == 2) {
+        v3 g = gen_quad(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), &R.seeds[i]);
+        R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
+      }
+    }
+  }
+  soa_record(&R, n, dep, 8, rec);
+  if (passes & (1u << 9)) {
+    /* SphereGenerateDir */
+    OMP_FOR FOR_RAYS {
+      if (R.which[i] == 3) {
+        v3 g = gen_sphere(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), &R.seeds[i]);
+        R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
+      }
+    }
+  }
+  soa_record(&R, n, dep, 9, rec);
+  if (passes & (1u << 10)) {
+    /* QuadPdf */
+    OMP_FOR FOR_RAYS {
+      if (R.status[i] & 8)
+        R.sum[i] += weight * quad_pdf_value(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), mk(R.gx[i], R.gy[i], R.gz[i]));
+    }
+  }
+  soa_record(&R, n, dep, 10, rec);
+  if (passes & (1u << 11)) {
+    /* SpherePdf */
+    OMP_FOR FOR_RAYS {
+      if (R.status[i] & 8) {
+        (void)rtpo_randf(&R.seeds[i]);
+        R.sum[i] += weight * sphere_pdf_value(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), mk(R.gx[i], R.gy[i], R.gz[i]));
+      }
+    }
+  }
+  soa_record(&R, n, dep, 11, rec);
+  if (passes & (1u << 12)) {
+    /* PDFCosineWorklet */
+    OMP_FOR FOR_RAYS {
+      uint8_t st = R.status[i];
+      if (!(st & 2)) {
+        v3 atten = mk(1.0f, 1.0f, 1.0f);
+        v3 oo = mk(R.ox[i], R.oy[i], R.oz[i]), od = mk(R.dx[i], R.dy[i], R.dz[i]);
+        if (st & 8) {
+          if (st & 16) {
+            atten = mk(R.sax[i], R.say[i], R.saz[i]);
+            oo = mk(R.sox[i], R.soy[i], R.soz[i]);
+            od = mk(R.sdx[i], R.sdy[i], R.sdz[i]);
+          } else {
+            v3 nn = mk(R.hnx[i], R.hny[i], R.hnz[i]);
+            v3 g = mk(R.gx[i], R.gy[i], R.gz[i]);
+            onb uvw = build_from_w(nn);
+            oo = mk(R.hpx[i], R.hpy[i], R.hpz[i]);
+            od = g;
+            float cv;
+            {
+              float cosine = dot(unit_vector(g), uvw.w);
+              cv = (cosine > 0) ? (float)(cosine / PI_D) : 0;
+            }
+            double pdf_val = 0.5 * R.sum[i] + 0.5 * cv;
+            float sp;
+            {
+              float cosine = dot(nn, unit_vector(od));
+              sp = (cosine < 0) ? 0 : (float)(cosine / PI_D);
+            }
+            double sctr = sp / pdf_val;
+            atten = mk((float)(R.sax[i] * sctr), (float)(R.say[i] * sctr), (float)(R.saz[i] * sctr));
+          }
+        }
+        Ax[i] = atten.x, Ay[i] = atten.y, Az[i] = atten.z;
+        R.ox[i] = oo.x, R.oy[i] = oo.y, R.oz[i] = oo.z;
+        R.dx[i] = od.x, R.dy[i] = od.y, R.dz[i] = od.z;
+      }
+      R.status[i] = (uint8_t)(st & ~(st >> 3));
+    }
+  }
+  soa_record(&R, n, dep, 12, rec);
+}
+
 int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
                         int32_t depth, uint32_t seed_base, int32_t row_begin, int32_t row_end, float* out_rgba,
                         uint32_t* out_seed, uint32_t* out_live, int32_t nthreads) {
@@ -870,21 +1147,8 @@ int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, i
   const int64_t first = (int64_t)row_begin * nx;
   const int64_t n = (int64_t)(row_end - row_begin) * nx;
   soa_t R;
-  float** fl[] = {&R.ox, &R.oy, &R.oz, &R.dx, &R.dy, &R.dz, &R.ht, &R.hnx, &R.hny, &R.hnz, &R.hpx, &R.hpy,
-                  &R.hpz, &R.sox, &R.soy, &R.soz, &R.sdx, &R.sdy, &R.sdz, &R.sax, &R.say, &R.saz, &R.gx, &R.gy,
-                  &R.gz, &R.sum, &R.tmin, &R.tx, &R.ty, &R.tz};
-  for (size_t k = 0; k < sizeof(fl) / sizeof(fl[0]); k++) *fl[k] = (float*)calloc(n, sizeof(float));
-  float** dl[] = {&R.Ax, &R.Ay, &R.Az, &R.Ex, &R.Ey, &R.Ez};
-  for (size_t k = 0; k < 6; k++) *dl[k] = (float*)calloc(n * depth, sizeof(float));
-  R.status = (uint8_t*)calloc(n, 1);
-  R.hm = (int32_t*)calloc(n, 4);
-  R.htx = (int32_t*)calloc(n, 4);
-  R.which = (int32_t*)calloc(n, 4);
-  R.seeds = (uint32_t*)calloc(n, 4);
-  R.live = (uint32_t*)calloc(n, 4);
+  soa_alloc(&R, n, depth);
   float* cols = (float*)calloc(n * 3, sizeof(float));
-  const float weight = (float)(1.0 / (float)2);
-  const float tmin_c = (float)0.001;
   /* seeds[i] = i (MapperPathTracer.cxx:265-267) */
   OMP_FOR FOR_RAYS R.seeds[i] = seed_base + (uint32_t)(first + i);
   for (int s = 0; s < spp; s++) {
@@ -895,180 +1159,7 @@ int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, i
       R.ox[i] = cam[0], R.oy[i] = cam[1], R.oz[i] = cam[2];
       R.status[i] = 1u << 3;
     }
-    for (int dep = 0; dep < depth; dep++) {
-      float* Ax = R.Ax + (int64_t)dep * n;
-      float* Ay = R.Ay + (int64_t)dep * n;
-      float* Az = R.Az + (int64_t)dep * n;
-      float* Ex = R.Ex + (int64_t)dep * n;
-      float* Ey = R.Ey + (int64_t)dep * n;
-      float* Ez = R.Ez + (int64_t)dep * n;
-      OMP_FOR FOR_RAYS { R.sum[i] = 0; R.ht[i] = FLT_MAX; R.tmin[i] = tmin_c; }
-      /* quad traversal (BVHTraverser over QuadLeafIntersector) */
-      OMP_FOR FOR_RAYS {
-        if (R.status[i] & 8) R.live[i]++;
-        if (!(R.status[i] & 8)) continue;
-        v3 o = mk(R.ox[i], R.oy[i], R.oz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
-        float closest = R.ht[i];
-        int hit = 0;
-        for (int q = 0; q < sc->n_quads; q++) {
-          const int32_t* id = sc->quad_ids[q];
-          hitrec tmp;
-          if (quad_intersect(o, d, R.tmin[i], closest, ld(sc->points[id[1]]), ld(sc->points[id[2]]),
-                             ld(sc->points[id[3]]), ld(sc->points[id[4]]), &tmp)) {
-            R.ht[i] = tmp.t;
-            R.hnx[i] = tmp.n.x, R.hny[i] = tmp.n.y, R.hnz[i] = tmp.n.z;
-            R.hpx[i] = tmp.p.x, R.hpy[i] = tmp.p.y, R.hpz[i] = tmp.p.z;
-            R.hm[i] = sc->quad_mat[q];
-            R.htx[i] = sc->quad_tex[q];
-            closest = tmp.t;
-            hit = 1;
-          }
-        }
-        R.status[i] |= (uint8_t)(hit << 2);
-        R.ht[i] = hit ? closest : FLT_MAX;
-      }
-      /* sphere traversal */
-      OMP_FOR FOR_RAYS {
-        if (!(R.status[i] & 8)) continue;
-        v3 o = mk(R.ox[i], R.oy[i], R.oz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
-        float closest = R.ht[i];
-        int hit = 0;
-        for (int k = 0; k < sc->n_spheres; k++) {
-          hitrec tmp;
-          if (sphere_hit(o, d, R.tmin[i], closest, ld(sc->points[sc->sphere_point[k]]), sc->sphere_radius[k],
-                         &tmp)) {
-            closest = tmp.t;
-            R.hnx[i] = tmp.n.x, R.hny[i] = tmp.n.y, R.hnz[i] = tmp.n.z;
-            R.hpx[i] = tmp.p.x, R.hpy[i] = tmp.p.y, R.hpz[i] = tmp.p.z;
-            R.hm[i] = sc->sphere_mat[k];
-            R.htx[i] = sc->sphere_tex[k];
-            hit = 1;
-          }
-        }
-        R.status[i] |= (uint8_t)(hit << 2);
-        if ((R.status[i] & 8) && (R.status[i] & 4)) R.ht[i] = closest;
-      }
-      /* CollectIntersecttWorklet */
-      OMP_FOR FOR_RAYS {
-        uint8_t st = R.status[i];
-        if (!((st & 8) && (st & 4))) {
-          st &= (uint8_t)~8u;
-          Ax[i] = 1.0f, Ay[i] = 1.0f, Az[i] = 1.0f;
-          Ex[i] = 0.0f, Ey[i] = 0.0f, Ez[i] = 0.0f;
-        }
-        st &= (uint8_t)~4u;
-        R.status[i] = st;
-      }
-      /* LambertianWorklet */
-      OMP_FOR FOR_RAYS {
-        uint8_t st = R.status[i];
-        if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 0) {
-          const float* c = sc->tex[sc->tex_type[R.htx[i]]];
-          R.sax[i] = c[0], R.say[i] = c[1], R.saz[i] = c[2];
-          R.status[i] = (uint8_t)((st | 8u) & ~16u);
-          Ex[i] = 0, Ey[i] = 0, Ez[i] = 0;
-        }
-      }
-      /* DiffuseLightWorklet */
-      OMP_FOR FOR_RAYS {
-        uint8_t st = R.status[i];
-        if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 1) {
-          const float* c = sc->tex[sc->tex_type[R.htx[i]]];
-          v3 nn = mk(R.hnx[i], R.hny[i], R.hnz[i]), d = mk(R.dx[i], R.dy[i], R.dz[i]);
-          int em = dot(nn, d) < 0.0;
-          Ex[i] = em ? c[0] : 0, Ey[i] = em ? c[1] : 0, Ez[i] = em ? c[2] : 0;
-          R.status[i] = 0; /* fin &= (false << 3) */
-        }
-      }
-      /* DielectricWorklet */
-      OMP_FOR FOR_RAYS {
-        uint8_t st = R.status[i];
-        if (!(st & 2) && (st & 8) && sc->mat_type[R.hm[i]] == 2) {
-          float r = rtpo_randf(&R.seeds[i]);
-          v3 so, sd;
-          dielectric_scatter(mk(R.dx[i], R.dy[i], R.dz[i]), mk(R.hnx[i], R.hny[i], R.hnz[i]),
-                             mk(R.hpx[i], R.hpy[i], R.hpz[i]), sc->ior, r, &so, &sd);
-          R.sax[i] = 1, R.say[i] = 1, R.saz[i] = 1;
-          R.sox[i] = so.x, R.soy[i] = so.y, R.soz[i] = so.z;
-          R.sdx[i] = sd.x, R.sdy[i] = sd.y, R.sdz[i] = sd.z;
-          R.status[i] = (uint8_t)(st | 8u | 16u);
-          Ex[i] = 0, Ey[i] = 0, Ez[i] = 0;
-        }
-      }
-      /* WhichGenerateDir (all rays) */
-      OMP_FOR FOR_RAYS R.which[i] = which_of(rtpo_randf(&R.seeds[i]));
-      /* CosineGenerateDir */
-      OMP_FOR FOR_RAYS {
-        if (R.which[i] <= 1) {
-          v3 g = gen_cosine(mk(R.hnx[i], R.hny[i], R.hnz[i]), &R.seeds[i]);
-          R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
-        }
-      }
-      /* QuadGenerateDir */
-      OMP_FOR FOR_RAYS {
-        if (R.which[i] == 2) {
-          v3 g = gen_quad(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), &R.seeds[i]);
-          R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
-        }
-      }
-      /* SphereGenerateDir */
-      OMP_FOR FOR_RAYS {
-        if (R.which[i] == 3) {
-          v3 g = gen_sphere(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), &R.seeds[i]);
-          R.gx[i] = g.x, R.gy[i] = g.y, R.gz[i] = g.z;
-        }
-      }
-      /* QuadPdf */
-      OMP_FOR FOR_RAYS {
-        if (R.status[i] & 8)
-          R.sum[i] += weight * quad_pdf_value(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), mk(R.gx[i], R.gy[i], R.gz[i]));
-      }
-      /* SpherePdf */
-      OMP_FOR FOR_RAYS {
-        if (R.status[i] & 8) {
-          (void)rtpo_randf(&R.seeds[i]);
-          R.sum[i] += weight * sphere_pdf_value(&L, mk(R.hpx[i], R.hpy[i], R.hpz[i]), mk(R.gx[i], R.gy[i], R.gz[i]));
-        }
-      }
-      /* PDFCosineWorklet */
-      OMP_FOR FOR_RAYS {
-        uint8_t st = R.status[i];
-        if (!(st & 2)) {
-          v3 atten = mk(1.0f, 1.0f, 1.0f);
-          v3 oo = mk(R.ox[i], R.oy[i], R.oz[i]), od = mk(R.dx[i], R.dy[i], R.dz[i]);
-          if (st & 8) {
-            if (st & 16) {
-              atten = mk(R.sax[i], R.say[i], R.saz[i]);
-              oo = mk(R.sox[i], R.soy[i], R.soz[i]);
-              od = mk(R.sdx[i], R.sdy[i], R.sdz[i]);
-            } else {
-              v3 nn = mk(R.hnx[i], R.hny[i], R.hnz[i]);
-              v3 g = mk(R.gx[i], R.gy[i], R.gz[i]);
-              onb uvw = build_from_w(nn);
-              oo = mk(R.hpx[i], R.hpy[i], R.hpz[i]);
-              od = g;
-              float cv;
-              {
-                float cosine = dot(unit_vector(g), uvw.w);
-                cv = (cosine > 0) ? (float)(cosine / PI_D) : 0;
-              }
-              double pdf_val = 0.5 * R.sum[i] + 0.5 * cv;
-              float sp;
-              {
-                float cosine = dot(nn, unit_vector(od));
-                sp = (cosine < 0) ? 0 : (float)(cosine / PI_D);
-              }
-              double sctr = sp / pdf_val;
-              atten = mk((float)(R.sax[i] * sctr), (float)(R.say[i] * sctr), (float)(R.saz[i] * sctr));
-            }
-          }
-          Ax[i] = atten.x, Ay[i] = atten.y, Az[i] = atten.z;
-          R.ox[i] = oo.x, R.oy[i] = oo.y, R.oz[i] = oo.z;
-          R.dx[i] = od.x, R.dy[i] = od.y, R.dz[i] = od.z;
-        }
-        R.status[i] = (uint8_t)(st & ~(st >> 3));
-      }
-    }
+    for (int dep = 0; dep < depth; dep++) soa_depth(sc, &L, &R, n, dep, nthreads, RTPO_PASS_ALL, NULL);
     /* backward SliceTransform passes (MapperPathTracer.cxx:328-348) */
     {
       const int64_t off = (int64_t)(depth - 1) * n;
@@ -1106,10 +1197,278 @@ int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, i
     if (out_seed) out_seed[i] = R.seeds[i];
     if (out_live) out_live[i] = R.live[i];
   }
-  for (size_t k = 0; k < sizeof(fl) / sizeof(fl[0]); k++) free(*fl[k]);
-  for (size_t k = 0; k < 6; k++) free(*dl[k]);
-  free(R.status), free(R.hm), free(R.htx), free(R.which), free(R.seeds), free(R.live), free(cols);
+  soa_free(&R);
+  free(cols);
   return 0;
+}
+
+/* One depth of the stage-structured variant from given rays (rtp_oracle.h) */
+void rtpo_bounce(const rtpo_scene* sc, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out) {
+  lights L;
+  setup_lights(sc, &L);
+  soa_t R;
+  soa_alloc(&R, n, 1);
+  FOR_RAYS {
+    R.ox[i] = rays[6 * i + 0], R.oy[i] = rays[6 * i + 1], R.oz[i] = rays[6 * i + 2];
+    R.dx[i] = rays[6 * i + 3], R.dy[i] = rays[6 * i + 4], R.dz[i] = rays[6 * i + 5];
+    R.seeds[i] = seeds[i];
+    R.status[i] = 1u << 3;
+  }
+  soa_depth(sc, &L, &R, n, 0, 1, RTPO_PASS_ALL, out);
+  soa_free(&R);
+}
+
+/* ------------------------------------------------------- stage exports ---
+ * Thin entry points over the static functions above, one per stage of
+ * tests/cpp/ref_stage_driver.cpp and in its word layouts (tests/_ref_cases.py
+ * STAGES), so that each can be held to the reference's recorded results. */
+typedef union {
+  uint32_t u;
+  int32_t i;
+  float f;
+} word;
+static inline v3 ldw(const word* w) { return mk(w[0].f, w[1].f, w[2].f); }
+static inline void stw(word* w, v3 a) { w[0].f = a.x, w[1].f = a.y, w[2].f = a.z; }
+
+/* the bilinear (u, v) of QuadLeafIntersector::hit, Surface.h:106-158, which
+ * quad_hit omits: computed for a ray that hit() accepts */
+static void quad_uv(v3 o, v3 d, v3 v00, v3 v10, v3 v11, v3 v01, float* u_out, float* v_out) {
+  v3 E03 = sub(v01, v00);
+  v3 P = cross(d, E03);
+  v3 E01 = sub(v10, v00);
+  float inv_det = 1.0f / dot(E01, P);
+  v3 T = sub(o, v00);
+  float alpha = dot(T, P) * inv_det;
+  v3 Q = cross(T, E01);
+  float beta = dot(d, Q) * inv_det;
+  float alpha_11, beta_11, u, v;
+  v3 E02 = sub(v11, v00);
+  v3 n = cross(E01, E02);
+  if ((fabsf(n.x) >= fabsf(n.y)) && (fabsf(n.x) >= fabsf(n.z))) {
+    alpha_11 = ((E02.y * E03.z) - (E02.z * E03.y)) / n.x;
+    beta_11 = ((E01.y * E02.z) - (E01.z * E02.y)) / n.x;
+  } else if ((fabsf(n.y) >= fabsf(n.x)) && (fabsf(n.y) >= fabsf(n.z))) {
+    alpha_11 = ((E02.z * E03.x) - (E02.x * E03.z)) / n.y;
+    beta_11 = ((E01.z * E02.x) - (E01.x * E02.z)) / n.y;
+  } else {
+    alpha_11 = ((E02.x * E03.y) - (E02.y * E03.x)) / n.z;
+    beta_11 = ((E01.x * E02.y) - (E01.y * E02.x)) / n.z;
+  }
+  if (fabsf(alpha_11 - 1.0f) < EPS_F) {
+    u = alpha;
+    if (fabsf(beta_11 - 1.0f) < EPS_F)
+      v = beta;
+    else
+      v = beta / ((u * (beta_11 - 1.0f)) + 1.0f);
+  } else if (fabs(beta_11 - 1.0) < EPS_F) { /* Surface.h:140: this one is compared in double */
+    v = beta;
+    u = alpha / ((v * (alpha_11 - 1.0f)) + 1.0f);
+  } else {
+    float A = 1.0f - beta_11;
+    float B = (alpha * (beta_11 - 1.0f)) - (beta * (alpha_11 - 1.0f)) - 1.0f;
+    float C = alpha;
+    float D = (B * B) - (4.0f * A * C);
+    float QQ = -0.5f * (B + ((B < 0.0f ? -1.0f : 1.0f) * sqrtf(D)));
+    u = QQ / A;
+    if ((u < 0.0f) || (u > 1.0f)) u = C / QQ;
+    v = beta / ((u * (beta_11 - 1.0f)) + 1.0f);
+  }
+  *u_out = u;
+  *v_out = v;
+}
+
+void rtpo_stage_rng(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    word* o = (word*)out + 3 * i;
+    uint32_t s = in[i];
+    o[0].u = rtpo_wang32(in[i]);
+    o[1].f = rtpo_randf(&s);
+    o[2].u = s;
+  }
+}
+void rtpo_stage_which(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    uint32_t s = in[i];
+    out[2 * i] = (uint32_t)which_of(rtpo_randf(&s));
+    out[2 * i + 1] = s;
+  }
+}
+void rtpo_stage_onb(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    const word* w = (const word*)in + 6 * i;
+    word* o = (word*)out + 12 * i;
+    onb b = build_from_w(ldw(w));
+    stw(o, b.u), stw(o + 3, b.v), stw(o + 6, b.w), stw(o + 9, local(&b, ldw(w + 3)));
+  }
+}
+static void put_hit(word* o, int h, const hitrec* r) {
+  o[0].i = h;
+  o[1].f = h ? r->t : 0;
+  stw(o + 2, h ? r->n : mk(0, 0, 0));
+  stw(o + 5, h ? r->p : mk(0, 0, 0));
+}
+void rtpo_stage_quad_hit(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    const word* w = (const word*)in + 20 * i;
+    word* o = (word*)out + 12 * i;
+    v3 org = ldw(w), d = ldw(w + 3), v00 = ldw(w + 6), v10 = ldw(w + 9), v11 = ldw(w + 12), v01 = ldw(w + 15);
+    float t = 0, u = 0, v = 0;
+    int h = quad_hit(org, d, v00, v10, v11, v01, &t);
+    if (h) quad_uv(org, d, v00, v10, v11, v01, &u, &v);
+    o[0].i = h, o[1].f = h ? u : 0, o[2].f = h ? v : 0, o[3].f = h ? t : 0;
+    hitrec rec;
+    put_hit(o + 4, quad_intersect(org, d, w[18].f, w[19].f, v00, v10, v11, v01, &rec), &rec);
+  }
+}
+void rtpo_stage_sphere_hit(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    const word* w = (const word*)in + 12 * i;
+    hitrec rec;
+    put_hit((word*)out + 8 * i, sphere_hit(ldw(w), ldw(w + 3), w[10].f, w[11].f, ldw(w + 6), w[9].f, &rec), &rec);
+  }
+}
+/* The stages below run one pass of soa_depth -- the code rtpo_render_soa runs -- on n one-ray
+ * states loaded from the case words. */
+typedef struct {
+  soa_t R;
+  lights L;
+  int64_t n;
+} stage_t;
+static void stage_open(stage_t* S, const rtpo_scene* sc, int64_t n) {
+  S->n = n;
+  setup_lights(sc, &S->L);
+  soa_alloc(&S->R, n, 1);
+}
+static void stage_run(stage_t* S, const rtpo_scene* sc, uint32_t passes) {
+  soa_depth(sc, &S->L, &S->R, S->n, 0, 1, passes, NULL);
+}
+static void ld3(float* x, float* y, float* z, int64_t i, const word* w) { x[i] = w[0].f, y[i] = w[1].f, z[i] = w[2].f; }
+static void st3(word* o, const float* x, const float* y, const float* z, int64_t i) {
+  o[0].f = x[i], o[1].f = y[i], o[2].f = z[i];
+}
+
+/* the three material worklets' operator(), EmitWorklet.h:46-73, 112-135, 244-272 (passes 3-5) */
+void rtpo_stage_material(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out) {
+  for (int kind = 0; kind < 3; kind++) {
+    stage_t S;
+    stage_open(&S, sc, n);
+    soa_t R = S.R;
+    FOR_RAYS {
+      const word* w = (const word*)in + 20 * i;
+      R.status[i] = (uint8_t)w[1].i;
+      ld3(R.ox, R.oy, R.oz, i, w + 2), ld3(R.dx, R.dy, R.dz, i, w + 5);
+      R.ht[i] = w[10].f;
+      ld3(R.hnx, R.hny, R.hnz, i, w + 11), ld3(R.hpx, R.hpy, R.hpz, i, w + 14);
+      R.hm[i] = w[17].i, R.htx[i] = w[18].i;
+      R.seeds[i] = w[19].u;
+    }
+    stage_run(&S, sc, 1u << (3 + kind));
+    FOR_RAYS {
+      if (((const word*)in)[20 * i].i != kind) continue;
+      word* o = (word*)out + 14 * i;
+      o[0].u = R.status[i];
+      st3(o + 1, R.sox, R.soy, R.soz, i), st3(o + 4, R.sdx, R.sdy, R.sdz, i), st3(o + 7, R.sax, R.say, R.saz, i);
+      st3(o + 10, R.Ex, R.Ey, R.Ez, i);
+      o[13].u = R.seeds[i];
+    }
+    soa_free(&S.R);
+  }
+}
+void rtpo_stage_dielectric_scatter(const uint32_t* in, int64_t n, uint32_t* out) {
+  FOR_RAYS {
+    const word* w = (const word*)in + 12 * i;
+    word* o = (word*)out + 9 * i;
+    uint64_t bits = (uint64_t)w[9].u | ((uint64_t)w[10].u << 32);
+    double rnd;
+    memcpy(&rnd, &bits, 8);
+    v3 so, sd;
+    dielectric_scatter(ldw(w), ldw(w + 3), ldw(w + 6), w[11].f, rnd, &so, &sd);
+    stw(o, so), stw(o + 3, sd), stw(o + 6, mk(1, 1, 1)); /* EmitWorklet.h:182-184 */
+  }
+}
+/* the three generator worklets' operator(), PdfWorklet.h:63-79, 112-137, 193-213 (passes 7-9) */
+void rtpo_stage_generator(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out) {
+  for (int kind = 0; kind < 3; kind++) {
+    stage_t S;
+    stage_open(&S, sc, n);
+    soa_t R = S.R;
+    FOR_RAYS {
+      const word* w = (const word*)in + 9 * i;
+      R.which[i] = w[1].i;
+      ld3(R.hnx, R.hny, R.hnz, i, w + 2), ld3(R.hpx, R.hpy, R.hpz, i, w + 5);
+      R.seeds[i] = w[8].u;
+    }
+    stage_run(&S, sc, 1u << (7 + kind));
+    FOR_RAYS {
+      if (((const word*)in)[9 * i].i != kind) continue;
+      word* o = (word*)out + 4 * i;
+      st3(o, R.gx, R.gy, R.gz, i);
+      o[3].u = R.seeds[i];
+    }
+    soa_free(&S.R);
+  }
+}
+/* QuadPDFWorklet and SpherePDFWorklet operator(), PdfWorklet.h:274-316, 374-399 (passes 10, 11) */
+void rtpo_stage_light_pdf(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out) {
+  for (int kind = 0; kind < 2; kind++) {
+    stage_t S;
+    stage_open(&S, sc, n);
+    soa_t R = S.R;
+    FOR_RAYS {
+      const word* w = (const word*)in + 10 * i;
+      R.status[i] = (uint8_t)w[1].i;
+      ld3(R.hpx, R.hpy, R.hpz, i, w + 2), ld3(R.gx, R.gy, R.gz, i, w + 5);
+      R.sum[i] = w[8].f;
+      R.seeds[i] = w[9].u;
+    }
+    stage_run(&S, sc, 1u << (10 + kind));
+    FOR_RAYS {
+      if (((const word*)in)[10 * i].i != kind) continue;
+      word* o = (word*)out + 2 * i;
+      o[0].f = R.sum[i];
+      o[1].u = R.seeds[i];
+    }
+    soa_free(&S.R);
+  }
+}
+/* PDFCosineWorklet::operator(), ScatterWorklet.h:79-116 (pass 12) */
+void rtpo_stage_scatter(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out) {
+  stage_t S;
+  stage_open(&S, sc, n);
+  soa_t R = S.R;
+  FOR_RAYS {
+    const word* w = (const word*)in + 26 * i;
+    R.status[i] = (uint8_t)w[0].i;
+    ld3(R.ox, R.oy, R.oz, i, w + 1), ld3(R.dx, R.dy, R.dz, i, w + 4);
+    ld3(R.hnx, R.hny, R.hnz, i, w + 7), ld3(R.hpx, R.hpy, R.hpz, i, w + 10);
+    ld3(R.sox, R.soy, R.soz, i, w + 13), ld3(R.sdx, R.sdy, R.sdz, i, w + 16), ld3(R.sax, R.say, R.saz, i, w + 19);
+    R.sum[i] = w[22].f;
+    ld3(R.gx, R.gy, R.gz, i, w + 23);
+  }
+  stage_run(&S, sc, 1u << 12);
+  FOR_RAYS {
+    word* o = (word*)out + 10 * i;
+    o[0].u = R.status[i];
+    st3(o + 1, R.ox, R.oy, R.oz, i), st3(o + 4, R.dx, R.dy, R.dz, i), st3(o + 7, R.Ax, R.Ay, R.Az, i);
+  }
+  soa_free(&S.R);
+}
+/* CollectIntersecttWorklet::operator(), SurfaceWorklets.h:104-109 (pass 2); 7 marks "left alone" */
+void rtpo_stage_collect(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out) {
+  stage_t S;
+  stage_open(&S, sc, n);
+  soa_t R = S.R;
+  FOR_RAYS {
+    R.status[i] = (uint8_t)in[i];
+    R.Ex[i] = R.Ey[i] = R.Ez[i] = R.Ax[i] = R.Ay[i] = R.Az[i] = 7.0f;
+  }
+  stage_run(&S, sc, 1u << 2);
+  FOR_RAYS {
+    word* o = (word*)out + 7 * i;
+    o[0].u = R.status[i];
+    st3(o + 1, R.Ex, R.Ey, R.Ez, i), st3(o + 4, R.Ax, R.Ay, R.Az, i);
+  }
+  soa_free(&S.R);
 }
 
 /* NormalizeFunctor, main.cc:253-287 (alpha is normalised too; rgb de-NaN'd) */

@@ -7,15 +7,26 @@
  * by tests/ (as the parity checker), by __graft_entry__.smoke() (checker) and
  * by bench.py's cpu_baseline leg (timed CPU baseline, kind "port").
  *
- * Parity status: PARITY UNPINNED against the reference itself.  The reference
- * cannot be compiled here (needs VTK-m, absent) and holds no
- * tests, golden images or fixtures for this path, so this restatement is only
- * partially pinned, by (i) known-answer tests
- * probed on this host (RNG, glibc sinf/cosf bit-exactness, g++ argument
- * evaluation order) and (ii) the two internal variants (scalar per-pixel and
- * stage-structured SoA) agreeing bit-for-bit.  VTK-m behaviour that the
- * reference relies on is restated from its published semantics and each
- * assumption is listed in DESIGN.md section "Oracle assumptions".
+ * Parity status: pinned to the reference's own worklets, stage by stage.  The
+ * whole reference cannot be compiled here (it needs VTK-m, absent, see
+ * SURVEY.md 8c), but its header-only worklets (PdfWorklet.h, EmitWorklet.h,
+ * ScatterWorklet.h, SurfaceWorklets.h, Surface.h, onb.h, wangXor.h, vec3.h)
+ * compile unchanged over tests/cpp/vtkm_min/ and are executed by
+ * tests/cpp/ref_stage_driver.cpp; their recorded results
+ * (tests/golden/ref_stages.npz) are what tests/test_ref_stages.py holds the
+ * rtpo_stage_* exports and rtpo_bounce below to, bit for bit.
+ *   Pinned: every arithmetic expression of those worklets (RNG, which, onb,
+ *   quad and sphere hit, the three materials, the dielectric's scatter, the
+ *   three generators, both light pdfs, PDFCosineWorklet, CollectIntersectt-
+ *   Worklet), each alone and in the order of one depth of RenderCellsImpl.
+ *   Still restated only: the VTK-m helpers (as tests/cpp/vtkm_min/ states
+ *   them), LinearBVH leaf order, the per-depth glue of RenderCellsImpl, the
+ *   backward product, ray generation (Camera.cxx; Worklets.h's RayGen is a
+ *   different text), the scene builder and everything of -direct mode.
+ * Each assumption is listed in DESIGN.md section 2, "Oracle assumptions".
+ * Further pins: known-answer tests probed on this host (RNG, glibc sinf/cosf
+ * bit-exactness) and the two internal variants (scalar per-pixel and
+ * stage-structured SoA) agreeing bit-for-bit.
  */
 #ifndef RTP_ORACLE_H
 #define RTP_ORACLE_H
@@ -151,6 +162,38 @@ void rtpo_render_direct(const rtpo_scene* sc, const rtpo_direct_cam* cam, const 
 
 /* NormalizeFunctor (main.cc:253-287): de-NaN rgb, then sqrt(x / spp). */
 void rtpo_normalize(float* rgba, int64_t n, int32_t spp);
+
+/* ---------------------------------------------------------------------
+ * Stage exports: what tests/test_ref_stages.py holds to the results the
+ * reference's own worklet headers produced (tests/golden/ref_stages.npz,
+ * recorded by oracle/_ref/ref_stages = tests/cpp/ref_stage_driver.cpp).
+ * Cases and results are rows of 32-bit words (float bits, int32 or uint32)
+ * in the layouts of tests/_ref_cases.py STAGES; n rows in, n rows out.  The
+ * stages that take a scene run the matching pass of the stage-structured
+ * variant (rtpo_render_soa's own code) on one-ray states. */
+void rtpo_stage_rng(const uint32_t* in, int64_t n, uint32_t* out);               /* getWang32; getRandF */
+void rtpo_stage_which(const uint32_t* in, int64_t n, uint32_t* out);             /* WorketletGenerateDir */
+void rtpo_stage_onb(const uint32_t* in, int64_t n, uint32_t* out);               /* build_from_w + local */
+void rtpo_stage_quad_hit(const uint32_t* in, int64_t n, uint32_t* out);          /* hit and intersect */
+void rtpo_stage_sphere_hit(const uint32_t* in, int64_t n, uint32_t* out);        /* SphereLeafIntersector::hit */
+void rtpo_stage_dielectric_scatter(const uint32_t* in, int64_t n, uint32_t* out); /* DielectricWorklet::scatter */
+void rtpo_stage_material(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
+void rtpo_stage_generator(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
+void rtpo_stage_light_pdf(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
+void rtpo_stage_scatter(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out); /* PDFCosineWorklet */
+void rtpo_stage_collect(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
+
+/* One depth (depth 0) of the stage-structured variant for n rays given as
+ * rays[6*i..] = origin, direction and seeds[i], all alive (Status = 8) over
+ * zeroed buffers.  out[(i*RTPO_BOUNCE_PASSES + c)*RTPO_BOUNCE_WORDS ..] is
+ * ray i's state after pass c (quad traversal, sphere traversal, collect,
+ * lambertian, diffuse light, dielectric, which, cosine / quad / sphere
+ * generator, quad pdf, sphere pdf, PDFCosineWorklet): status; hit record T,
+ * N, P; hit ids M, T; scatter record O, D, A; which; generated direction;
+ * sum_value; emitted[0]; attenuation[0]; origin; direction; seed. */
+#define RTPO_BOUNCE_PASSES 13
+#define RTPO_BOUNCE_WORDS 37
+void rtpo_bounce(const rtpo_scene* sc, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out);
 
 /* primitives, exported for known-answer tests */
 uint32_t rtpo_wang32(uint32_t seed);

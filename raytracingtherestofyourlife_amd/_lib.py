@@ -87,6 +87,7 @@ EXPORTED_SYMBOLS = [
     "rtp_last_error", "rtp_abi_version", "rtp_create", "rtp_destroy", "rtp_set_scene", "rtp_render",
     "rtp_render_device", "rtp_render_tiles_device", "rtp_render_pixels", "rtp_normalize", "rtp_write_pnm", "rtp_cornell_box",
     "rtp_eval_primitive", "rtp_debug_counters", "rtp_verify_fast_math", "rtp_debug_closest_hit",
+    "rtp_debug_bounce",
     "rtp_render_direct", "rtp_render_direct_device", "rtp_sample_color_table", "rtp_quad_scalars",
     "rtp_cornell_point_field", "rtp_write_pnm_depth", "rtp_eval_powf", "rtp_set_ff_tables", "rtp_get_ff_tables",
     "rtp_render_planned_device", "rtp_sphere_walk", "rtp_sphere_walk_oct_mask",
@@ -204,6 +205,11 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
         L.rtp_resolve.argtypes = [vp, f32p, f32p, i32p, ctypes.c_int32, ctypes.c_int64, f32p, stp]
         L.rtp_denoise_device.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dpp, vp, vp, vp, stp]
         L.rtp_denoise.argtypes = [vp, f32p, f32p, f32p, ctypes.c_int32, ctypes.c_int32, dpp, f32p, stp]
+    # (likewise a revision before rtp_debug_bounce: the parent build a change is timed against)
+    if bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_debug_bounce"):
+        skip += ("rtp_debug_bounce",)
+    else:
+        L.rtp_debug_bounce.argtypes = [vp, vp, vp, ctypes.c_int64, vp]
     L.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
     L.rtp_get_ff_tables.argtypes = [vp, ctypes.POINTER(RtpFfInfo)]
     L.rtp_sphere_walk.argtypes = [vp]

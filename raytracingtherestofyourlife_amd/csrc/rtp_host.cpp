@@ -39,6 +39,8 @@ extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, fl
                                         rtp::BvhNode* d_nodes, rtp::DevSphereG* d_geom, hipStream_t stream);
 extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const float* rays, uint32_t* out,
                                               int64_t n, int bvh, hipStream_t stream);
+extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const float* rays, const uint32_t* seeds,
+                                             uint32_t* out, int64_t n, int bvh, hipStream_t stream);
 extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
                                         hipStream_t stream);
 extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
@@ -1651,6 +1653,25 @@ rtp_status rtp_debug_closest_hit(rtp_context* c, const float* rays, int64_t n, u
   HIP_TRY_AS("rtp_debug_closest_hit", b.get(&dout, (size_t)n * 28));
   HIP_TRY_AS("rtp_debug_closest_hit", rtp_launch_eval_closest(c->d_scene, din, dout, n, c->use_bvh ? 1 : 0, nullptr));
   HIP_TRY_AS("rtp_debug_closest_hit", DevBufs::back(out, dout, (size_t)n * 28));
+  return RTP_OK;
+}
+
+// Diagnostics: one depth of the path kernel's bounce() for host rays and
+// seeds (rtp_eval_bounce_kernel; 15 u32 per ray).
+rtp_status rtp_debug_bounce(rtp_context* c, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out) {
+  if (!c || !rays || !seeds || !out || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_bounce: bad arguments");
+  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "rtp_debug_bounce: no scene set");
+  if (n == 0) return RTP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  DevBufs b;
+  float* din = nullptr;
+  uint32_t* dseed = nullptr;
+  uint32_t* dout = nullptr;
+  HIP_TRY_AS("rtp_debug_bounce", b.get(&din, (size_t)n * 24, rays));
+  HIP_TRY_AS("rtp_debug_bounce", b.get(&dseed, (size_t)n * 4, seeds));
+  HIP_TRY_AS("rtp_debug_bounce", b.get(&dout, (size_t)n * 60));
+  HIP_TRY_AS("rtp_debug_bounce", rtp_launch_eval_bounce(c->d_scene, din, dseed, dout, n, c->use_bvh ? 1 : 0, nullptr));
+  HIP_TRY_AS("rtp_debug_bounce", DevBufs::back(out, dout, (size_t)n * 60));
   return RTP_OK;
 }
 

@@ -1639,6 +1639,42 @@ __global__ void __launch_bounds__(256) rtp_eval_closest_kernel(const DevScene* _
   w[6] = full;
 }
 
+// One bounce() per host ray (o, d: 6 floats; its seed), one lane per ray:
+// depth 0 of a two-deep path, so that A[0] is stored.  out[15 i ..] = the
+// result code, emit, A[0], ps.org, ps.dir, the seed after the depth's draws,
+// ps.nonfinite.  emit starts as 0 and A[0] as 1: what the reference's
+// arrays hold after a depth that ends the path (SurfaceWorklets.h:104-109,
+// ScatterWorklet.h:80, 114).
+template <bool kBvh>
+__global__ void __launch_bounds__(256) rtp_eval_bounce_kernel(const DevScene* __restrict__ sc,
+                                                              const float* __restrict__ rays,
+                                                              const uint32_t* __restrict__ seeds, uint32_t* out,
+                                                              int64_t n) {
+  __shared__ __align__(16) float s_qshade[kQTableFloats];
+  fill_qshade(sc, s_qshade);
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * i;
+  Path ps;
+  ps.org = mk(r[0], r[1], r[2]);
+  ps.dir = mk(r[3], r[4], r[5]);
+  ps.d = 0;
+  ps.nonfinite = false;
+  uint32_t seed = seeds[i];
+  f3 emit = mk(0.f, 0.f, 0.f);
+  float4 a0 = make_float4(1.f, 1.f, 1.f, 0.f);
+  const int res = bounce<kBvh, false>(sc, ps, seed, emit, &a0, 2, nullptr, s_qshade);
+  uint32_t* w = out + 15 * i;
+  w[0] = (uint32_t)res;
+  w[1] = __float_as_uint(emit.x), w[2] = __float_as_uint(emit.y), w[3] = __float_as_uint(emit.z);
+  w[4] = __float_as_uint(a0.x), w[5] = __float_as_uint(a0.y), w[6] = __float_as_uint(a0.z);
+  w[7] = __float_as_uint(ps.org.x), w[8] = __float_as_uint(ps.org.y), w[9] = __float_as_uint(ps.org.z);
+  w[10] = __float_as_uint(ps.dir.x), w[11] = __float_as_uint(ps.dir.y), w[12] = __float_as_uint(ps.dir.z);
+  w[13] = seed;
+  w[14] = ps.nonfinite ? 1u : 0u;
+}
+
 // First-hit guides of a path camera (rtp_render_guides_device), one lane per
 // pixel: the ray through the pixel centre (camera_ray_at with 0.5f for both
 // jitter draws), the path kernel's closest_hit, and of that hit the normal
@@ -1912,6 +1948,14 @@ extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const 
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
   if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_closest_kernel<true>, g, b, 0, stream, scene, rays, out, n);
   else hipLaunchKernelGGL(rtp::rtp_eval_closest_kernel<false>, g, b, 0, stream, scene, rays, out, n);
+  return hipGetLastError();
+}
+extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const float* rays, const uint32_t* seeds,
+                                             uint32_t* out, int64_t n, int bvh, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const dim3 g((unsigned)((n + 255) / 256)), b(256);
+  if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<true>, g, b, 0, stream, scene, rays, seeds, out, n);
+  else hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<false>, g, b, 0, stream, scene, rays, seeds, out, n);
   return hipGetLastError();
 }
 extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves,

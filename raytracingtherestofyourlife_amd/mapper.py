@@ -570,6 +570,20 @@ class Device:
                                             out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def debug_bounce(self, rays: np.ndarray, seeds: np.ndarray) -> np.ndarray:
+        """(n, 6) float32 rays (o, d) and (n,) uint32 RNG states -> (n, 15)
+        uint32, one depth of the path kernel's bounce: result (0 goes on, 1
+        missed, 2 light), emitted, attenuation[0], next origin, next
+        direction (float bits), the RNG state after the depth, non-finite flag."""
+        a = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if s.shape[0] != a.shape[0]:
+            raise ValueError("debug_bounce: one seed per ray")
+        out = np.zeros((a.shape[0], 15), dtype=np.uint32)
+        check(self._L.rtp_debug_bounce(self.handle, a.ctypes.data_as(ctypes.c_void_p), s.ctypes.data_as(ctypes.c_void_p),
+                                       a.shape[0], out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
 
 # ------------------------------------------------------------- mapper --
 class MapperPathTracer:

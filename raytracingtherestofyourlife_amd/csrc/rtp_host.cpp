@@ -24,10 +24,12 @@
 #include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
 
-extern "C" int64_t rtp_plan_history_lanes(int64_t npix, int spp, int bvh, int* variant_out, int* waves_out);
+extern "C" const char* rtp_instance_name(int variant, int stats, int walk, int tiles, int plan, int steal, int views,
+                                         int resume);
+extern "C" int64_t rtp_plan_history_lanes(int64_t npix, int spp, int bvh, int stats, int* variant_out, int* waves_out);
 extern "C" int rtp_plan_steal(int64_t npix, int bvh);
 extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves, int bvh,
-                                        hipStream_t stream, int lds_bytes);
+                                        int stats, int steal, hipStream_t stream, int lds_bytes);
 extern "C" int rtp_lds_walk_capacity(void);
 extern "C" hipError_t rtp_launch_eval_primitive(int kind, const void* in, void* out, int64_t n, const uint32_t* tab,
                                                 uint32_t t1, uint32_t t2, hipStream_t stream);
@@ -1105,6 +1107,7 @@ struct LaunchPlan {
   int variant = 2, waves = 0, bvh = 0;  // bvh: the sphere walk (plan_launch)
   int64_t lanes = 0;                    // history lanes
   bool stats_on = false, dbg = false;   // RTP_DEBUG_STATS=1: the diagnostics build; 1 or 2: per-wave counters
+  bool steal = false;                   // the resident waves steal entries (rtp_plan_steal gave `waves`)
 };
 
 rtp_status plan_launch(rtp_context* c, const RenderJob& j, LaunchPlan& pl) {
@@ -1116,9 +1119,12 @@ rtp_status plan_launch(rtp_context* c, const RenderJob& j, LaunchPlan& pl) {
   const char stats_env = env_char("RTP_DEBUG_STATS");
   pl.stats_on = stats_env == '1';
   pl.dbg = stats_env == '1' || stats_env == '2';  // 2: timestamps in the production kernel
-  // (a resume pass has no LDS-walk instance: the global walk, same results)
-  pl.bvh = !c->use_bvh ? 0 : (c->lw_bytes > 0 && !pl.stats_on && !j.d_wave_begin && !j.resume) ? 2 : 1;
-  pl.lanes = rtp_plan_history_lanes(j.npix, j.spp, pl.bvh, &pl.variant, &pl.waves);
+  // (a launch whose mode has no LDS-walk instance -- a resume pass, say --
+  // takes the global walk, same results: the instance table answers)
+  const bool lds_walk = c->lw_bytes > 0 && rtp_instance_name(2, pl.stats_on, 2, j.tile != nullptr, j.d_wave_begin != nullptr,
+                                                             0, j.d_views != nullptr, j.resume) != nullptr;
+  pl.bvh = !c->use_bvh ? 0 : lds_walk ? 2 : 1;
+  pl.lanes = rtp_plan_history_lanes(j.npix, j.spp, pl.bvh, pl.stats_on, &pl.variant, &pl.waves);
   if (j.d_wave_begin) {  // a planned launch: the caller's waves
     if (pl.variant != 2 || c->use_bvh || j.tile)
       return fail(RTP_ERR_INVALID_ARGUMENT, "render: a wave plan needs the pool kernel, no BVH, no tile deal");
@@ -1130,6 +1136,7 @@ rtp_status plan_launch(rtp_context* c, const RenderJob& j, LaunchPlan& pl) {
   if (pl.variant == 2 && !j.d_wave_begin && !pl.stats_on && j.spp > 0) {
     const int sw = env_is("RTP_STEAL", '0') ? 0 : rtp_plan_steal(j.npix, pl.bvh);
     if (sw > 0) {
+      pl.steal = true;
       pl.waves = sw;
       pl.lanes = (int64_t)sw * 128;
     }
@@ -1174,7 +1181,7 @@ rtp_status launch(rtp_context* c, const RenderJob& j) {
     p.dbg = c->d_dbg;
   }
   return timed_launch(c, j.stream, j.kernel_ms, true, [&]() -> rtp_status {
-    HIP_TRY(rtp_launch_render(c->d_scene, &p, pl.variant, pl.waves, pl.bvh, j.stream, c->lw_bytes));
+    HIP_TRY(rtp_launch_render(c->d_scene, &p, pl.variant, pl.waves, pl.bvh, pl.stats_on, pl.steal, j.stream, c->lw_bytes));
     return RTP_OK;
   });
 }

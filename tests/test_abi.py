@@ -116,7 +116,7 @@ def test_package_refuses_to_run_without_library(tmp_path, monkeypatch):
 
 def test_pool_kernel_reads_kparams_at_its_kernarg_offset(tmp_path):
     """rtp_render_pool re-reads KParams through the kernarg segment pointer at
-    byte offset kKParamsOffset = 8 (rtp_kernels.hip kparams()): check that
+    byte offset kKParamsOffset = 8 (rtp_pool.hpp kparams()): check that
     against the argument metadata of the gfx950 code object in librtp.so."""
     import shutil
 

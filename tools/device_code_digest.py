@@ -4,7 +4,13 @@ kernels' instructions) and of its .rodata (the kernel descriptors: register
 and LDS budgets).  Two builds whose listings agree run the same kernels, so a
 host-only change can be checked without a GPU:
 
-    python tools/device_code_digest.py [path/to/librtp.so ...]
+    python tools/device_code_digest.py [--per-kernel] [path/to/librtp.so ...]
+
+--per-kernel: instead, one row per symbol, sorted by name: the SHA-256 of
+every function's bytes in .text and of every kernel descriptor (*.kd, 64
+bytes of .rodata) with its kernel_code_entry_byte_offset zeroed.  A change
+that only reorders the kernels inside a code object changes the section
+digests and leaves these rows as they were.
 
 Only these two sections are hashed: the fat binary as a whole also carries
 build-identifier bytes that differ between two builds of the same sources.
@@ -75,6 +81,45 @@ def elf_sections(elf: bytes) -> dict:
     return out
 
 
+def elf_symbols(elf: bytes):
+    """(name, section name, bytes, type) of every defined symbol of .symtab
+    whose bytes lie in a section with contents"""
+    (shoff,) = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", elf, 0x3A)
+    heads = [struct.unpack_from("<IIQQQQI", elf, shoff + i * shentsize) for i in range(shnum)]
+    shnames = elf[heads[shstrndx][4]:heads[shstrndx][4] + heads[shstrndx][5]]
+    label = lambda h: shnames[h[0]:shnames.index(b"\0", h[0])].decode()
+    out = []
+    for h in heads:
+        if h[1] != 2:  # SHT_SYMTAB
+            continue
+        stroff = heads[h[6]][4]  # (sh_link: its string table)
+        for at in range(h[4], h[4] + h[5], 24):
+            name, info, _other, shndx, value, size = struct.unpack_from("<IBBHQQ", elf, at)
+            if not 0 < shndx < shnum or heads[shndx][1] == 8 or size == 0:
+                continue
+            sec = heads[shndx]
+            start = sec[4] + value - sec[3]  # file offset: section offset + (address - section address)
+            out.append((elf[stroff + name:elf.index(b"\0", stroff + name)].decode(), label(sec),
+                        elf[start:start + size], info & 15))
+    return out
+
+
+def per_kernel(elf: bytes):
+    """Sorted (symbol, sha256): every function symbol of .text by its code
+    bytes, every *.kd kernel descriptor of .rodata by its 64 bytes with
+    kernel_code_entry_byte_offset (bytes 16-23: where the kernel lies in
+    .text relative to the descriptor) zeroed.  Equal rows mean equal kernels
+    wherever the linker put them."""
+    rows = []
+    for name, sec, data, kind in elf_symbols(elf):
+        if sec == ".text" and kind == 2:  # STT_FUNC
+            rows.append((name, hashlib.sha256(data).hexdigest()))
+        elif sec == ".rodata" and name.endswith(".kd") and len(data) == 64:
+            rows.append((name, hashlib.sha256(data[:16] + bytes(8) + data[24:]).hexdigest()))
+    return sorted(rows)
+
+
 def digest(lib: str):
     rows = []
     for bundle, ident, elf in code_objects(fatbin(lib)):
@@ -84,7 +129,14 @@ def digest(lib: str):
 
 
 if __name__ == "__main__":
-    for lib in sys.argv[1:] or [DEFAULT_LIB]:
+    args = [a for a in sys.argv[1:] if a != "--per-kernel"]
+    for lib in args or [DEFAULT_LIB]:
         print(lib)
+        if "--per-kernel" in sys.argv[1:]:
+            for bundle, ident, elf in code_objects(fatbin(lib)):
+                print(f"  [{bundle}] {ident}")
+                for name, sha in per_kernel(elf):
+                    print(f"      {sha}  {name}")
+            continue
         for bundle, ident, text, rodata in digest(lib):
             print(f"  [{bundle}] {ident}\n      .text   {text}\n      .rodata {rodata}")

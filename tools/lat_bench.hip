@@ -4,7 +4,7 @@
 // Each lane runs a chain of bounces in the C2 scene (Cornell box, variant 0):
 // a random ray from a random point inside the room, then from each hit point
 // on: closest_hit (+ shade_hit: material, generator, pdfs, scatter) exactly as
-// the render kernel runs them (the device functions of rtp_kernels.hip,
+// the render kernel runs them (the device functions of rtp_trace.hpp,
 // included below).  A path that dies restarts from a random point.  W waves
 // per SIMD (grid = CUs x W blocks of 4 waves): W = 1 gives a lone wave's
 // latency per step, W = 5 the pool kernel's occupancy.
@@ -37,9 +37,12 @@
 //        -I raytracingtherestofyourlife_amd/csrc tools/lat_bench.hip
 //        -L raytracingtherestofyourlife_amd -lrtp -Wl,-rpath,<that dir> -o tools/lat_bench
 // usage: tools/lat_bench [iters] [modes...]
-#include "../raytracingtherestofyourlife_amd/csrc/rtp_kernels.hip"
+#include "../raytracingtherestofyourlife_amd/csrc/rtp_trace.hpp"
 #include "../raytracingtherestofyourlife_amd/csrc/rtp_context.hpp"
 
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 namespace lb {

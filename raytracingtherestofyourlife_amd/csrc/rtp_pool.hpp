@@ -137,17 +137,46 @@ constexpr int kWavesPerBlock = 4;
 constexpr int kPool = RTP_POOL;  // pixel slots per wave (power of two: queue index = cursor & (kPool-1))
 static_assert(kPool == kPoolSlots || RTP_POOL != 128, "rtp_layout.hpp kPoolSlots is the production pool size");
 static_assert((kPool & (kPool - 1)) == 0 && kPool >= 64, "pool size must be a power of two >= 64");
-// LDS per wave: seed, r, g, b, samples, live (u32) + rem, q_ready, q_ff (u16):
-// 30 B x 128 slots x 4 waves + the 2 KB quad shading table = 17 KiB per
-// block.  Occupancy is set by VGPRs (5 waves per SIMD at <= 96, below).
+// A wave's pool in LDS: one array of kPool per field, in this order (the
+// 32-bit fields first, so every array is aligned).  The pixel's RNG state,
+// colour sums, finished samples and live-bounce count; the remaining dead
+// depths of its finished sample; the READY and fast-forward rings (of slots).
+#define RTP_POOL_SLOT_FIELDS(F)                                                                       \
+  F(uint32_t, seed) F(float, r) F(float, g) F(float, b) F(uint32_t, samples) F(uint32_t, live) \
+  F(uint16_t, rem) F(uint16_t, q_ready) F(uint16_t, q_ff)
+struct PoolSlots {
+#define F(T, name) T* name;
+  RTP_POOL_SLOT_FIELDS(F)
+#undef F
+  uint32_t* entry;  // kSteal: the slot's entry    } the wave's part of a table of the block,
+  float* m2;        // kResume: its second moment  } null in the other instances
+};
+// LDS per wave: 30 B x 128 slots x 4 waves + the 2 KB quad shading table =
+// 17 KiB per block.  Occupancy is set by VGPRs (5 waves per SIMD at <= 96, below).
 // Measured on C2 / C3 / C4: 128 slots at 5 waves beat 256 slots at 4 waves
 // by 6 / 10 / 5%; 256 slots at 5 waves (LDS booked to the last byte) and
 // 128 slots at 6 waves (80 VGPRs, spills) were slower.
-constexpr int kSlotBytes = 6 * 4 + 3 * 2;
-// s_rem packs the remaining dead depths with how the sample's path ended
+#define F(T, name) +(int)sizeof(T)
+constexpr int kSlotBytes = 0 RTP_POOL_SLOT_FIELDS(F);
+#undef F
+static_assert(kSlotBytes == 30, "the measured pool: 30 B per slot");
+constexpr int pool_lds_bytes(int waves) { return waves * kPool * kSlotBytes; }  // a block's pools
+constexpr int entry_lds_bytes(int waves) { return waves * kPool * (int)sizeof(*PoolSlots().entry); }  // its entry table
+// s_entry_all (kSteal) and s_m2_all (kResume): the block's tables
+template <class Cfg>
+RTP_DEV PoolSlots pool_slots(unsigned char* smem, int wib, uint32_t* s_entry_all, float* s_m2_all) {
+  PoolSlots s;
+  unsigned char* at = smem + (size_t)wib * kPool * kSlotBytes;
+#define F(T, name) s.name = reinterpret_cast<T*>(at), at += kPool * sizeof(T);
+  RTP_POOL_SLOT_FIELDS(F)
+#undef F
+  s.entry = Cfg::kSteal ? s_entry_all + wib * kPool : nullptr;
+  s.m2 = Cfg::kResume ? s_m2_all + wib * kPool : nullptr;
+  return s;
+}
+// PoolSlots::rem packs the remaining dead depths with how the sample's path ended
 constexpr int kRemMask = 0x3fff, kEndLight = 0x4000, kEndNonfinite = 0x8000;
-static_assert(kMaxDepth <= kRemMask, "the remaining dead depths fit s_rem's count field");
-constexpr int kPoolLdsBytes = kWavesPerBlock * kPool * kSlotBytes;
+static_assert(kMaxDepth <= kRemMask, "the remaining dead depths fit rem's count field");
 
 RTP_DEV uint32_t lane_rank(uint64_t mask) {  // number of set mask bits below this lane
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -203,9 +232,9 @@ typedef const __attribute__((address_space(1))) uint32_t GU32;
 // state arrays (KParams::out, seed_out, live_out, m2) where the other
 // instances compute or zero them, and written back by the unchanged write-out:
 // each entry is owned by one slot, read once before its first sample of the
-// pass and written once after its last.  s_samples counts the pass's samples.
-// The second moment of the samples' luminance runs in a fifth float per slot
-// (s_m2_all), added where the sample is added to the sums.
+// pass and written once after its last.  PoolSlots::samples counts the pass's
+// samples.  The second moment of the samples' luminance runs in a fifth float
+// per slot (PoolSlots::m2), added where the sample is added to the sums.
 // One instance's modes, by name (the seven of rtp_render_pool's template
 // signature, in its order); LdsBvh: rtp_render_pool_lds's 16-wave block.
 template <bool Stats, bool Bvh, bool Tiles, bool Plan, bool Steal, bool Views, bool Resume, bool LdsBvh = false>
@@ -214,6 +243,110 @@ struct PoolCfg {
                         kResume = Resume, kLdsBvh = LdsBvh;
   static constexpr int kWPB = LdsBvh ? kLdsBvhWavesPerBlock : kWavesPerBlock;  // waves per block
 };
+
+// A wave's place in the launch (wave-uniform): its global id, the launch's
+// waves, (kPlan) its first entry, and the slots that hold an entry at the deal.
+struct PoolWave {
+  int w, n_waves, wbase, n_slots;
+};
+// slot j of wave w <-> list entry k = j * n_waves + w (pixels interleaved over waves)
+// or, planned, k = wave_begin[w] + j.  Idx: the deal and the write-outs index
+// with 64 bits, the refill with 32 (a 64-bit index spilled there).
+template <class Cfg, class Idx>
+RTP_DEV Idx dealt_entry(const PoolWave& wv, int slot) {
+  return Cfg::kPlan ? (Idx)(wv.wbase + slot) : (Idx)slot * wv.n_waves + wv.w;
+}
+template <class Cfg, class Idx>
+RTP_DEV Idx entry_of(const PoolSlots& s, const PoolWave& wv, int slot) {  // (kSteal: the entry the slot claimed last)
+  if constexpr (Cfg::kSteal) return (Idx)s.entry[slot];
+  else return dealt_entry<Cfg, Idx>(wv, slot);
+}
+
+// Slot j writes its entry k out, after the entry's last sample of the launch.
+// (Its counterpart, a slot taking an entry, stays written out at the deal and
+// at the steal claim: as one function it moved the code of 12 instances.)
+template <class Cfg>
+RTP_DEV void slot_write(const KParams& p, const PoolSlots& s, int j, int64_t k) {
+  reinterpret_cast<float4*>(p.out)[k] = make_float4(s.r[j], s.g[j], s.b[j], 0.f);
+  if (p.seed_out) p.seed_out[k] = s.seed[j];
+  if (p.live_out) p.live_out[k] = s.live[j];
+  if constexpr (Cfg::kResume)
+    if (p.m2) p.m2[k] = s.m2[j];
+}
+
+// Back-to-front radiance of a sample that ended on the light at depth k_end
+// (path_radiance), from the slot's history rows (row k_end holds E).
+// Rows k_end and k_end-1 .. k_end-5 issued together (clamped to row 0; rows
+// below 0 are not applied), the rest kHistChunk per trip, each chunk's loads
+// issued together (one wait per chunk); products in the reference's order
+// (depth k_end-1 down to 0).  One wait instead of up to three dependent round
+// trips: C2 -1% (r03f, profiles/r03f_ab_history_prefetch.txt).
+// (The masked multiply stays written out twice: as a helper of its own it
+// moved the code of every pool instance.)
+RTP_DEV f3 light_radiance(const float4* hist_base, int slot, int k_end, int64_t stride) {
+  const float4* __restrict__ hp = hist_base + slot;
+  f3 rw[kHistPrefetch];
+#pragma unroll
+  for (int i = 0; i < kHistPrefetch; i++) {
+    const float4 v = hp[(int64_t)max(k_end - i, 0) * stride];
+    rw[i] = mk(v.x, v.y, v.z);
+  }
+  float sx = rw[0].x + 0.0f, sy = rw[0].y + 0.0f, sz = rw[0].z + 0.0f;
+#pragma unroll
+  for (int i = 1; i < kHistPrefetch; i++) {
+    const bool on = k_end - i >= 0;
+    sx = on ? 0.0f + rw[i].x * sx : sx;
+    sy = on ? 0.0f + rw[i].y * sy : sy;
+    sz = on ? 0.0f + rw[i].z * sz : sz;
+  }
+  int dd = k_end - kHistPrefetch;
+  for (; dd >= 0; dd -= kHistChunk) {
+    f3 rc[kHistChunk];
+#pragma unroll
+    for (int i = 0; i < kHistChunk; i++) {
+      const float4 v = hp[(int64_t)max(dd - i, 0) * stride];
+      rc[i] = mk(v.x, v.y, v.z);
+    }
+#pragma unroll
+    for (int i = 0; i < kHistChunk; i++) {
+      const bool on = dd - i >= 0;
+      sx = on ? 0.0f + rc[i].x * sx : sx;
+      sy = on ? 0.0f + rc[i].y * sy : sy;
+      sz = on ? 0.0f + rc[i].z * sz : sz;
+    }
+  }
+  return mk(sx, sy, sz);
+}
+
+// The fast-forward's first jump-table read, issued before the radiance loads
+// so that its latency overlaps theirs: the direct table of the sample's
+// remaining count frc when there is one (then it is the only read), else the
+// 32-depth table.
+struct FfEarly {
+  bool direct, chain;  // which table was read, if any
+  uint32_t seed;
+};
+RTP_DEV FfEarly ff_early_read(bool mine, uint32_t fseed, int frc) {
+  FfEarly e;
+  e.seed = 0;
+  CKP& FP = kparams();
+  e.direct = mine && FP.ffd != nullptr && (unsigned)(frc - FP.ffd_first) < (unsigned)FP.ffd_count;
+  e.chain = mine && !e.direct && FP.ff[0] != nullptr && frc >= 32;
+  if (e.direct || e.chain) {
+    GU32* src = (GU32*)(e.direct ? FP.ffd + ((uint64_t)(frc - FP.ffd_first) << 32) : FP.ff[0]);
+    e.seed = src[fseed];
+  }
+  return e;
+}
+
+// The pool kernel's body: the deal, then the scheduling loop -- fast-forward
+// batch if due, refill, walk, shade, end, publish -- then the write-out.
+// The loop's stages stay inline and its state in plain locals.  As functions
+// of their own (a slot taking an entry, the table jumps and hash loop, the
+// primary ray, the walk, the priority block) or gathered into structs (the
+// scheduler's and the lane's state, a stats object) they changed the
+// instructions of the production instances, in every form tried; the helpers
+// above are the ones that left them byte for byte.
 // s_entry_all (kSteal) and s_m2_all (kResume): the block's tables, null in the other instances
 template <class Cfg>
 __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const KParams& p, int n_waves,
@@ -237,23 +370,10 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
   }
   __syncthreads();
   if (w >= n_waves) return;  // whole wave leaves; no block-level barriers follow
-  unsigned char* base = smem + (size_t)wib * kPool * kSlotBytes;
-  uint32_t* s_seed = reinterpret_cast<uint32_t*>(base);
-  float* s_r = reinterpret_cast<float*>(s_seed + kPool);
-  float* s_g = s_r + kPool;
-  float* s_b = s_g + kPool;
-  uint32_t* s_samples = reinterpret_cast<uint32_t*>(s_b + kPool);
-  uint32_t* s_live = s_samples + kPool;
-  uint16_t* s_rem = reinterpret_cast<uint16_t*>(s_live + kPool);
-  uint16_t* q_ready = s_rem + kPool;
-  uint16_t* q_ff = q_ready + kPool;
-  uint32_t* s_entry = kSteal ? s_entry_all + wib * kPool : nullptr;  // kSteal: the slot's entry
-  float* s_m2 = kResume ? s_m2_all + wib * kPool : nullptr;          // kResume: the slot's second moment
+  const PoolSlots s = pool_slots<Cfg>(smem, wib, s_entry_all, s_m2_all);
 
   const uint32_t t1 = sc->which_t1, t2 = sc->which_t2;
   const int D = p.depth, S = p.spp;
-  // slot j of wave w <-> list entry k = j * n_waves + w (pixels interleaved over waves)
-  // or, planned, k = wave_begin[w] + j
   int n_slots, wbase = 0;
   if constexpr (kPlan) {  // (the host checked the plan; the clamps keep a bad one inside the buffers)
     wbase = p.wave_begin[w];
@@ -262,29 +382,30 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     const int64_t left = p.npix - w;
     n_slots = left <= 0 ? 0 : (int)min<int64_t>(kPool, (left + n_waves - 1) / n_waves);
   }
-  for (int j = lane; j < n_slots; j += 64) {
-    const int64_t k = kPlan ? (int64_t)(wbase + j) : (int64_t)j * n_waves + w;
-    if constexpr (kSteal) s_entry[j] = (uint32_t)k;
+  const PoolWave wv{w, n_waves, wbase, n_slots};
+  for (int j = lane; j < n_slots; j += 64) {  // the deal: slot j takes its entry
+    const int64_t k = dealt_entry<Cfg, int64_t>(wv, j);
+    if constexpr (kSteal) s.entry[j] = (uint32_t)k;
     if constexpr (kResume) {  // the entry's state so far
       const float4 v = reinterpret_cast<const float4*>(p.out)[k];
-      s_seed[j] = p.seed_out[k];
-      s_r[j] = v.x;
-      s_g[j] = v.y;
-      s_b[j] = v.z;
-      s_samples[j] = 0u;
-      s_live[j] = p.live_out ? p.live_out[k] : 0u;
-      s_m2[j] = p.m2 ? p.m2[k] : 0.f;
+      s.seed[j] = p.seed_out[k];
+      s.r[j] = v.x;
+      s.g[j] = v.y;
+      s.b[j] = v.z;
+      s.samples[j] = 0u;
+      s.live[j] = p.live_out ? p.live_out[k] : 0u;
+      s.m2[j] = p.m2 ? p.m2[k] : 0.f;
     } else {
-      if constexpr (kViews) s_seed[j] = view_seed(p, (int)k);
-      else s_seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
-      s_r[j] = 0.f;
-      s_g[j] = 0.f;
-      s_b[j] = 0.f;
-      s_samples[j] = 0u;
-      s_live[j] = 0u;
+      if constexpr (kViews) s.seed[j] = view_seed(p, (int)k);
+      else s.seed[j] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, k);  // seeds[i] = i (MapperPathTracer.cxx:265-267)
+      s.r[j] = 0.f;
+      s.g[j] = 0.f;
+      s.b[j] = 0.f;
+      s.samples[j] = 0u;
+      s.live[j] = 0u;
     }
-    s_rem[j] = 0;
-    q_ready[j] = (uint16_t)j;
+    s.rem[j] = 0;
+    s.q_ready[j] = (uint16_t)j;
   }
   wave_sync();
   // wave-uniform, monotone queue cursors
@@ -337,7 +458,6 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
   // to its end inside one iteration); now a long walk no longer holds the
   // other 63 lanes.  The walk is the same walk (same nodes, same order, same
   // running minimum), so the hit is bit-identical.
-  constexpr bool kWalk = kBvh;
   int wni = -1;                             // the path's next BVH node; -1: its quads are not scanned yet
   Hit wh{3.40282347e+38f, -1, 0};           // its closest hit so far
   Path ps;
@@ -361,23 +481,11 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
       int fslot = 0, frem = 0;
       uint32_t fseed = 0;
       if (mine) {
-        fslot = q_ff[(ff_head + lane) & (kPool - 1)];
-        fseed = s_seed[fslot];
-        frem = s_rem[fslot];
+        fslot = s.q_ff[(ff_head + lane) & (kPool - 1)];
+        fseed = s.seed[fslot];
+        frem = s.rem[fslot];
       }
-      // the first jump-table read is issued before the radiance loads below,
-      // so its latency overlaps theirs: the direct table of the sample's
-      // remaining count when there is one (then it is the only read), else
-      // the 32-depth table
-      uint32_t early = 0;
-      const int frc = frem & kRemMask;
-      CKP& FP = kparams();
-      const bool has_direct = mine && FP.ffd != nullptr && (unsigned)(frc - FP.ffd_first) < (unsigned)FP.ffd_count;
-      const bool has_early = mine && !has_direct && FP.ff[0] != nullptr && frc >= 32;
-      if (has_direct || has_early) {
-        GU32* src = (GU32*)(has_direct ? FP.ffd + ((uint64_t)(frc - FP.ffd_first) << 32) : FP.ff[0]);
-        early = src[fseed];
-      }
+      const FfEarly early = ff_early_read(mine, fseed, frem & kRemMask);
       if (mine) {
         // back-to-front radiance of the pixel's finished sample (path_radiance),
         // banked in sample order before the pixel's next sample can start
@@ -390,65 +498,27 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
             dbg_region(gdbg, kDbgFfRadVisits);
             dbg_add(gdbg, kDbgFfRadRows, (unsigned long long)(k_end + 1));
           }
-          const float4* __restrict__ hp = hist_base + fslot;
-          // rows k_end (E) and k_end-1 .. k_end-5 issued together (clamped to
-          // row 0; rows below 0 are not applied), the rest two per trip;
-          // products in the reference's order (depth k_end-1 down to 0).
-          // One wait instead of up to three dependent round trips: C2 -1%
-          // (r03f, profiles/r03f_ab_history_prefetch.txt).
-          f3 rw[kHistPrefetch];
-#pragma unroll
-          for (int i = 0; i < kHistPrefetch; i++) {
-            const float4 v = hp[(int64_t)max(k_end - i, 0) * stride];
-            rw[i] = mk(v.x, v.y, v.z);
-          }
-          float sx = rw[0].x + 0.0f, sy = rw[0].y + 0.0f, sz = rw[0].z + 0.0f;
-#pragma unroll
-          for (int i = 1; i < kHistPrefetch; i++) {
-            const bool on = k_end - i >= 0;
-            sx = on ? 0.0f + rw[i].x * sx : sx;
-            sy = on ? 0.0f + rw[i].y * sy : sy;
-            sz = on ? 0.0f + rw[i].z * sz : sz;
-          }
-          int dd = k_end - kHistPrefetch;
-          // the remaining rows kHistChunk at a time, each chunk's loads
-          // issued together (one wait per chunk)
-          for (; dd >= 0; dd -= kHistChunk) {
-            f3 rc[kHistChunk];
-#pragma unroll
-            for (int i = 0; i < kHistChunk; i++) {
-              const float4 v = hp[(int64_t)max(dd - i, 0) * stride];
-              rc[i] = mk(v.x, v.y, v.z);
-            }
-#pragma unroll
-            for (int i = 0; i < kHistChunk; i++) {
-              const bool on = dd - i >= 0;
-              sx = on ? 0.0f + rc[i].x * sx : sx;
-              sy = on ? 0.0f + rc[i].y * sy : sy;
-              sz = on ? 0.0f + rc[i].z * sz : sz;
-            }
-          }
-          c = mk(sx, sy, sz);
+          c = light_radiance(hist_base, fslot, k_end, stride);
         } else {
           const float v = (flags & kEndNonfinite) ? __builtin_nanf("") : 0.0f;
           c = mk(v, v, v);
         }
-        s_r[fslot] = s_r[fslot] + c.x;  // cols += sumtotl (MapperPathTracer.cxx:350), in sample order
-        s_g[fslot] = s_g[fslot] + c.y;
-        s_b[fslot] = s_b[fslot] + c.z;
+        s.r[fslot] = s.r[fslot] + c.x;  // cols += sumtotl (MapperPathTracer.cxx:350), in sample order
+        s.g[fslot] = s.g[fslot] + c.y;
+        s.b[fslot] = s.b[fslot] + c.z;
         if constexpr (kResume) {  // m2 += y * y, y the sample's luminance (include/rtp.h rtp_render_state)
           const float y = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
-          s_m2[fslot] = s_m2[fslot] + y * y;
+          s.m2[fslot] = s.m2[fslot] + y * y;
         }
       }
       // jump over 32 / 16 / 8 / 4 dead depths with one table read each
       // (HBM-resident tables of the dead-step map, built once per device),
       // then hash the few remaining depths
-      if (has_direct) {
-        fseed = early;
+      if (early.direct) {
+        fseed = early.seed;
         frem = 0;
-      } else if (has_early) {
-        fseed = early;
+      } else if (early.chain) {
+        fseed = early.seed;
         frem -= 32;
       }
 #pragma unroll
@@ -471,8 +541,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
         iters++;
       }
       bool again = false;
-      if (mine) s_seed[fslot] = fseed;
-      if (mine) again = s_samples[fslot] < (uint32_t)S;
+      if (mine) s.seed[fslot] = fseed;
+      if (mine) again = s.samples[fslot] < (uint32_t)S;
       if (want_dbg) unfinished -= __popcll(__ballot(mine && !again));
       if constexpr (kSteal) {
         // pixels with all their samples: written out, their slots take the
@@ -486,34 +556,29 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
           base = __shfl(base, 0) + (unsigned long long)n_waves * kPool;
           retired += (uint32_t)(nd * S);
           if (mine && !again) {
-            const int64_t k = (int64_t)s_entry[fslot];
-            reinterpret_cast<float4*>(p.out)[k] = make_float4(s_r[fslot], s_g[fslot], s_b[fslot], 0.f);
-            if (p.seed_out) p.seed_out[k] = s_seed[fslot];
-            if (p.live_out) p.live_out[k] = s_live[fslot];
-            if constexpr (kResume)
-              if (p.m2) p.m2[k] = s_m2[fslot];
+            slot_write<Cfg>(p, s, fslot, entry_of<Cfg, int64_t>(s, wv, fslot));
             const unsigned long long kn = base + lane_rank(done);
             if (kn < (unsigned long long)p.npix) {  // a fresh pixel in this slot, at the front of READY below
-              s_entry[fslot] = (uint32_t)kn;
+              s.entry[fslot] = (uint32_t)kn;
               if constexpr (kResume) {  // the claimed entry's state so far
                 const float4 v = reinterpret_cast<const float4*>(p.out)[kn];
-                s_seed[fslot] = p.seed_out[kn];
-                s_r[fslot] = v.x;
-                s_g[fslot] = v.y;
-                s_b[fslot] = v.z;
-                s_samples[fslot] = 0u;
-                s_live[fslot] = p.live_out ? p.live_out[kn] : 0u;
-                s_m2[fslot] = p.m2 ? p.m2[kn] : 0.f;
+                s.seed[fslot] = p.seed_out[kn];
+                s.r[fslot] = v.x;
+                s.g[fslot] = v.y;
+                s.b[fslot] = v.z;
+                s.samples[fslot] = 0u;
+                s.live[fslot] = p.live_out ? p.live_out[kn] : 0u;
+                s.m2[fslot] = p.m2 ? p.m2[kn] : 0.f;
               } else {
-                if constexpr (kViews) s_seed[fslot] = view_seed(p, (int)kn);
-                else s_seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
-                s_r[fslot] = 0.f;
-                s_g[fslot] = 0.f;
-                s_b[fslot] = 0.f;
-                s_samples[fslot] = 0u;
-                s_live[fslot] = 0u;
+                if constexpr (kViews) s.seed[fslot] = view_seed(p, (int)kn);
+                else s.seed[fslot] = p.seed_base + (uint32_t)pixel_of<kTiles>(p, (int)kn);
+                s.r[fslot] = 0.f;
+                s.g[fslot] = 0.f;
+                s.b[fslot] = 0.f;
+                s.samples[fslot] = 0u;
+                s.live[fslot] = 0u;
               }
-              s_rem[fslot] = 0;
+              s.rem[fslot] = 0;
               again = true;
             }
           }
@@ -528,12 +593,12 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
       // (17% of bounce steps with ~12 of 64 lanes live).
       // (samples * slots <= 2^23 * 2^7; ff_tail (no stealing) and ff_tail - retired (the
       // held pixels' finished samples) are <= 2^7 * spp: 32 bits suffice)
-      const bool urgent = again && (kSteal ? s_samples[fslot] * (uint32_t)live_slots <= (uint32_t)(ff_tail - retired)
-                                           : s_samples[fslot] * (uint32_t)n_slots <= (uint32_t)ff_tail);
+      const bool urgent = again && (kSteal ? s.samples[fslot] * (uint32_t)live_slots <= (uint32_t)(ff_tail - retired)
+                                           : s.samples[fslot] * (uint32_t)n_slots <= (uint32_t)ff_tail);
       const uint64_t pu = __ballot(urgent), pn = __ballot(again && !urgent);
       ready_head -= (uint32_t)__popcll(pu);
-      if (urgent) q_ready[(ready_head + lane_rank(pu)) & (kPool - 1)] = (uint16_t)fslot;
-      if (again && !urgent) q_ready[(ready_tail + lane_rank(pn)) & (kPool - 1)] = (uint16_t)fslot;
+      if (urgent) s.q_ready[(ready_head + lane_rank(pu)) & (kPool - 1)] = (uint16_t)fslot;
+      if (again && !urgent) s.q_ready[(ready_tail + lane_rank(pn)) & (kPool - 1)] = (uint16_t)fslot;
       ready_tail += __popcll(pn);
       ff_head += n;
       wave_sync();
@@ -554,8 +619,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
       const int r = (int)lane_rank(idle);
       if (r < take) {
         if (want_dbg) dbg_region(gdbg, kDbgRefillVisits);
-        slot = q_ready[(ready_head + r) & (kPool - 1)];
-        seed = s_seed[slot];
+        slot = s.q_ready[(ready_head + r) & (kPool - 1)];
+        seed = s.seed[slot];
         hist = hist_base + slot;
         // the camera and tile constants re-read from the kernel arguments
         // here (kparams): kept live through the loop they were SGPRs spilled
@@ -565,14 +630,13 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
         int pi, pj;
         if constexpr (kViews) {  // the entry's view: its camera gathered per lane
           int v, u;
-          view_split(P, kSteal ? (int)s_entry[slot] : slot * n_waves + w, v, u);
+          view_split(P, entry_of<Cfg, int>(s, wv, slot), v, u);
           view_pixel_xy(P, u, pi, pj);
           const DevCamera vc = P.views[v].cam;
           ps.dir = camera_ray(vc, pi, pj, P.nx, P.ny, seed);
           ps.org = ld3(vc.eye);
         } else {
-          pixel_xy<kTiles>(P, kSteal ? (int)s_entry[slot] : kPlan ? wbase + slot : slot * n_waves + w, pi,
-                           pj);  // (32-bit index: a 64-bit one spilled)
+          pixel_xy<kTiles>(P, entry_of<Cfg, int>(s, wv, slot), pi, pj);
           ps.dir = camera_ray(P.cam, pi, pj, P.nx, P.ny, seed);
           ps.org = ld3(P.cam.eye);
         }
@@ -584,12 +648,13 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     ready_head += take;
     if (!__any(has_path) && ff_tail == ff_head) break;  // nothing live, nothing READY, nothing to fast-forward
     if (want_dbg) dbg[kDbgCyclesRefill] += __builtin_amdgcn_s_memtime() - tb;
-    // ---- one depth of every live path ----
+    // ---- one depth of every live path: walk (sphere-BVH scenes), shade, end ----
     bool ended = false;
     const unsigned long long ta = stamp(want_dbg);
     unsigned long long tbnc = ta;
     bool shade = has_path;
-    if constexpr (kWalk) {
+    if constexpr (kBvh) {
+      // the resumable sphere-BVH walk; the lanes whose walk is done shade
       const int nn = kLdsBvh ? sc->n_lw_nodes : sc->n_nodes;
       if (has_path && wni < 0) {  // a new ray: the quads first (their hit bounds the walk)
         wh = closest_hit<false, false>(sc, ps.org, ps.dir, true, nullptr, s_qshade + kPrexLdsOffset);
@@ -630,7 +695,7 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     if (shade) {
       f3 emit = mk(0.f, 0.f, 0.f);
       int res;
-      if constexpr (kWalk) {
+      if constexpr (kBvh) {
         res = shade_hit<kBvh, true>(sc, ps, seed, emit, hist + (int64_t)ps.d * stride, D, s_qshade, wh,
                                     gdbg);  // (stats build: the region counters; nullptr otherwise)
         wni = -1;
@@ -649,10 +714,10 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
         // dead depths left: D-1-k_end, plus depth k_end's own draws when the
         // path died there (bounce<.., true> left them to the fast-forward)
         const int rem = D - 1 - k_end + (res != kAlive ? 1 : 0);
-        s_rem[slot] = (uint16_t)(rem | (res == kLight ? kEndLight : 0) | (ps.nonfinite ? kEndNonfinite : 0));
-        s_samples[slot] = s_samples[slot] + 1u;
-        s_live[slot] = s_live[slot] + (uint32_t)(k_end + 1);
-        s_seed[slot] = seed;
+        s.rem[slot] = (uint16_t)(rem | (res == kLight ? kEndLight : 0) | (ps.nonfinite ? kEndNonfinite : 0));
+        s.samples[slot] = s.samples[slot] + 1u;
+        s.live[slot] = s.live[slot] + (uint32_t)(k_end + 1);
+        s.seed[slot] = seed;
         ended = true;
         has_path = false;
       }
@@ -662,8 +727,9 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
       dbg[kDbgCyclesShade] += tbnc - ta;  // minus the intersect share, subtracted on the host
       dbg[kDbgCyclesEnd] += te - tbnc;
     }
+    // ---- the ended samples queue for the fast-forward; publish ----
     const uint64_t fin = __ballot(ended);
-    if (ended) q_ff[(ff_tail + lane_rank(fin)) & (kPool - 1)] = (uint16_t)slot;
+    if (ended) s.q_ff[(ff_tail + lane_rank(fin)) & (kPool - 1)] = (uint16_t)slot;
 #if RTP_CRIT_FF > 0
     // A pixel whose finished samples lag the wave's average by more than
     // RTP_CRIT_FF/1000 runs its sample chain on the critical path (its path
@@ -671,7 +737,7 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     // READY queue to run dry -- the batch runs in the next iteration.
     // (a scheduling heuristic: single precision is plenty; kSteal: fresh
     // pixels always lag, so no critical batches)
-    if (!kSteal && __ballot(ended && (float)(s_samples[slot] * (uint32_t)n_slots) * 1000.0f <
+    if (!kSteal && __ballot(ended && (float)(s.samples[slot] * (uint32_t)n_slots) * 1000.0f <
                               (float)ff_tail * (float)(1000 - RTP_CRIT_FF)))
       critical_ff = true;
 #endif
@@ -720,14 +786,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
       if (c != kDbgRealStart && c != kDbgHwId) p.dbg[(int64_t)w * kDbgCounters + c] = dbg[c];
   }
   wave_sync();
-  for (int j = lane; j < (kSteal ? 0 : n_slots); j += 64) {  // (kSteal: written as they finished)
-    const int64_t k = kPlan ? (int64_t)(wbase + j) : (int64_t)j * n_waves + w;
-    reinterpret_cast<float4*>(p.out)[k] = make_float4(s_r[j], s_g[j], s_b[j], 0.f);
-    if (p.seed_out) p.seed_out[k] = s_seed[j];
-    if (p.live_out) p.live_out[k] = s_live[j];
-    if constexpr (kResume)
-      if (p.m2) p.m2[k] = s_m2[j];
-  }
+  for (int j = lane; j < (kSteal ? 0 : n_slots); j += 64)  // (kSteal: written as they finished)
+    slot_write<Cfg>(p, s, j, entry_of<Cfg, int64_t>(s, wv, j));
 }
 
 #if RTP_POOL_MAX_VGPR > 0
@@ -742,7 +802,7 @@ __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_
   static_assert(!kViews || (!kStats && !kBvh && !kTiles && !kPlan), "batched views: the plain and stealing instances");
   static_assert(!kResume || (!kStats && !kTiles && !kPlan && !kViews),
                 "resume: {no BVH, global sphere walk} x {plain, stealing}; no stats, wave plan, tile deal or views");
-  __shared__ __align__(16) unsigned char smem[kPoolLdsBytes];
+  __shared__ __align__(16) unsigned char smem[pool_lds_bytes(kWavesPerBlock)];
   __shared__ __align__(16) float s_qshade[kQTableFloats];
   float* s_m2 = nullptr;
   uint32_t* s_entry = nullptr;
@@ -765,7 +825,7 @@ __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_
 template <bool kTiles, bool kSteal>
 __global__ void __launch_bounds__(64 * kLdsBvhWavesPerBlock, 1) __attribute__((amdgpu_num_vgpr(128)))
     rtp_render_pool_lds(const DevScene* __restrict__ sc, KParams p, int n_waves) {
-  __shared__ __align__(16) unsigned char smem[kLdsBvhWavesPerBlock * kPool * kSlotBytes];
+  __shared__ __align__(16) unsigned char smem[pool_lds_bytes(kLdsBvhWavesPerBlock)];
   __shared__ __align__(16) float s_qshade[kQTableFloats];
   extern __shared__ __align__(16) uint32_t s_dyn[];
   uint32_t* s_entry = nullptr;
@@ -777,8 +837,8 @@ __global__ void __launch_bounds__(64 * kLdsBvhWavesPerBlock, 1) __attribute__((a
                       /*Resume*/ false, /*LdsBvh*/ true>;
   pool_body<Cfg>(sc, p, n_waves, smem, s_qshade, s_dyn, s_entry, nullptr);
 }
-constexpr int kLdsWalkStaticBytes =
-    kLdsBvhWavesPerBlock * kPool * kSlotBytes + kQTableFloats * 4 + kLdsBvhWavesPerBlock * kPool * 4;
+constexpr int kLdsWalkStaticBytes = pool_lds_bytes(kLdsBvhWavesPerBlock) + kQTableFloats * (int)sizeof(float) +
+                                    entry_lds_bytes(kLdsBvhWavesPerBlock);
 constexpr int kLdsWalkDynBytes = 160 * 1024 - kLdsWalkStaticBytes;  // the tree's share of the CU's 160 KiB
 static_assert(kPool != 128 || kLdsWalkDynBytes >= 64 * 1024, "the LDS walk keeps room for a C3-size tree");
 

@@ -2,8 +2,9 @@
 m-kim/raytracingtherestofyourlife (MapperPathTracer::RenderCellsImpl) as HIP
 kernels for gfx950 behind a C ABI (include/rtp.h, librtp.so)."""
 from ._lib import LIB_PATH, RtpError, load  # noqa: F401
+from .device import Device  # noqa: F401
 from .mapper import (  # noqa: F401
-    Camera, CanvasRayTracer, CellSet, CornellBox, DataSet, Device, ErrorBadValue, MapperPathTracer,
+    Camera, CanvasRayTracer, CellSet, CornellBox, DataSet, ErrorBadValue, MapperPathTracer,
     Field, default_camera, hemisphere_cameras, normalize, runPath, runPathProgressive, runPathViews, save_pnm,
 )
 from .progressive import ProgressiveRender, noise_from_state, select_active, split_passes  # noqa: F401

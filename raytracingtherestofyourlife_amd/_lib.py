@@ -21,6 +21,7 @@ f32p = ctypes.POINTER(ctypes.c_float)
 i32p = ctypes.POINTER(ctypes.c_int32)
 u32p = ctypes.POINTER(ctypes.c_uint32)
 i64p = ctypes.POINTER(ctypes.c_int64)
+vp = ctypes.c_void_p  # rtp_context*, void*, and every device buffer: callers hold addresses
 
 
 class RtpCamera(ctypes.Structure):
@@ -83,24 +84,81 @@ class RtpFfInfo(ctypes.Structure):
                 ("auto_samples", ctypes.c_uint64), ("auto_samples_direct", ctypes.c_uint64)]
 
 
-EXPORTED_SYMBOLS = [
-    "rtp_last_error", "rtp_abi_version", "rtp_create", "rtp_destroy", "rtp_set_scene", "rtp_render",
-    "rtp_render_device", "rtp_render_tiles_device", "rtp_render_pixels", "rtp_normalize", "rtp_write_pnm", "rtp_cornell_box",
-    "rtp_eval_primitive", "rtp_debug_counters", "rtp_verify_fast_math", "rtp_debug_closest_hit",
-    "rtp_debug_bounce",
-    "rtp_render_direct", "rtp_render_direct_device", "rtp_sample_color_table", "rtp_quad_scalars",
-    "rtp_cornell_point_field", "rtp_write_pnm_depth", "rtp_eval_powf", "rtp_set_ff_tables", "rtp_get_ff_tables",
-    "rtp_render_planned_device", "rtp_sphere_walk", "rtp_sphere_walk_oct_mask",
-    "rtp_render_views_device", "rtp_render_views", "rtp_render_resume_device", "rtp_render_resume",
-    "rtp_render_guides_device", "rtp_render_guides", "rtp_resolve_device", "rtp_resolve", "rtp_denoise_device",
-    "rtp_denoise",
-]
+# rtp::DbgCounter (csrc/rtp_layout.hpp) in its order, then the extra slot
+# rtp_debug_counters fills on request: the longest wave lifetime.
+DEBUG_COUNTERS = ("bounce_steps", "bounce_lanes", "ff_phases", "ff_lanes", "ff_iters", "cycles_bounce",
+                  "cycles_ff", "cycles_total", "cycles_intersect", "cycles_bounce_call", "cycles_end",
+                  "cycles_refill", "real_start", "real_end", "hw_id", "tail_steps", "tail_lanes",
+                  "tail_cycles", "fallback_steps", "fallback_lanes", "refill_visits", "refill_lanes",
+                  "hit_visits", "hit_lanes", "gen_visits", "gen_lanes", "cycles_gen", "cycles_pdf", "end_visits",
+                  "end_lanes", "ffrad_visits", "ffrad_lanes", "ffrad_rows", "dead_lanes", "diel_visits", "diel_lanes",
+                  "cycles_diel", "light_visits", "light_lanes", "box_free_steps", "box_lanes",
+                  "max_wave_cycles")
+N_DBG_COUNTERS = len(DEBUG_COUNTERS) - 1  # rtp::kDbgCounters: the width of a per-wave record
+
+
+def _signatures() -> dict:
+    """Every function of include/rtp.h, in its order: name -> (restype, argtypes)."""
+    i32, u32, i64, st = ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int32  # st: rtp_status
+    P = ctypes.POINTER
+    u64p, d64p = P(ctypes.c_uint64), P(ctypes.c_double)
+    cam, stats, aux, state = P(RtpCamera), P(RtpStats), P(RtpPixelAux), P(RtpRenderState)
+    return {
+        "rtp_last_error": (ctypes.c_char_p, []),
+        "rtp_abi_version": (i32, []),
+        "rtp_create": (st, [i32, P(vp)]),
+        "rtp_destroy": (None, [vp]),
+        "rtp_set_scene": (st, [vp, P(RtpSceneDesc)]),
+        "rtp_render": (st, [vp, cam, i32, i32, i32, i32, u32, f32p, stats]),
+        "rtp_render_tiles_device": (st, [vp, cam, i32, i32, i32, i32, u32, i32, i32, vp, vp, stats]),
+        "rtp_render_device": (st, [vp, cam, i32, i32, i32, i32, u32, i64, i64, vp, vp, aux, vp, stats]),
+        "rtp_render_planned_device": (st, [vp, cam, i32, i32, i32, i32, u32, i64, i64, vp, vp, i32, vp, aux, vp,
+                                           stats]),
+        "rtp_render_pixels": (st, [vp, cam, i32, i32, i32, i32, u32, i64p, i64, f32p, aux, stats]),
+        "rtp_render_views_device": (st, [vp, P(RtpView), i32, i32, i32, i32, i32, vp, aux, vp, stats]),
+        "rtp_render_views": (st, [vp, P(RtpView), i32, i32, i32, i32, i32, f32p, stats]),
+        "rtp_render_resume_device": (st, [vp, cam, i32, i32, i32, i32, i64, i64, vp, state, vp, stats]),
+        "rtp_render_resume": (st, [vp, cam, i32, i32, i32, i32, i64p, i64, state, stats]),
+        "rtp_render_guides_device": (st, [vp, cam, i32, i32, vp, vp, vp, vp, stats]),
+        "rtp_render_guides": (st, [vp, cam, i32, i32, f32p, f32p, i32p, stats]),
+        "rtp_resolve_device": (st, [vp, vp, vp, vp, i32, i64, vp, vp, stats]),
+        "rtp_resolve": (st, [vp, f32p, f32p, i32p, i32, i64, f32p, stats]),
+        "rtp_denoise_device": (st, [vp, vp, vp, vp, i32, i32, P(RtpDenoiseParams), vp, vp, vp, stats]),
+        "rtp_denoise": (st, [vp, f32p, f32p, f32p, i32, i32, P(RtpDenoiseParams), f32p, stats]),
+        "rtp_normalize": (st, [f32p, i64, i32]),
+        "rtp_write_pnm": (st, [ctypes.c_char_p, f32p, i32, i32]),
+        "rtp_cornell_box": (st, [i32, P(RtpSceneDesc)]),
+        "rtp_render_direct": (st, [vp, cam, i32, i32, P(RtpDirectDesc), f32p, f32p, f32p, f32p, stats]),
+        "rtp_render_direct_device": (st, [vp, cam, i32, i32, P(RtpDirectDesc), vp, vp, vp, vp, vp, stats]),
+        "rtp_sample_color_table": (st, [d64p, i32, d64p, i32, d64p, i32, f32p]),
+        "rtp_quad_scalars": (st, [f32p, i32, i32p, i32, f32p]),
+        "rtp_cornell_point_field": (st, [i32, P(f32p), P(i32), P(i32p), P(i32)]),
+        "rtp_write_pnm_depth": (st, [ctypes.c_char_p, f32p, i32, i32]),
+        "rtp_eval_powf": (st, [vp, f32p, ctypes.c_float, f32p, i64]),
+        "rtp_set_ff_tables": (st, [vp, i32]),
+        "rtp_get_ff_tables": (st, [vp, P(RtpFfInfo)]),
+        "rtp_eval_primitive": (st, [vp, i32, vp, vp, i64]),
+        "rtp_debug_counters": (i32, [vp, u64p, i32]),
+        "rtp_debug_closest_hit": (st, [vp, vp, i64, vp]),
+        "rtp_debug_bounce": (st, [vp, vp, vp, i64, vp]),
+        "rtp_sphere_walk": (i32, [vp]),
+        "rtp_sphere_walk_oct_mask": (i32, [vp]),
+        "rtp_verify_fast_math": (st, [vp, i32, u32, u32, u64p, P(u32)]),
+    }
+
+
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = list(SIGNATURES)
 
 
 class RtpError(RuntimeError):
     def __init__(self, status: int, msg: str):
         super().__init__(f"rtp error {status}: {msg}")
         self.status = status
+
+
+class ErrorBadValue(ValueError):
+    """vtkm::cont::ErrorBadValue."""
 
 
 _lib = None
@@ -125,98 +183,21 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     except ImportError:
         pass
     L = ctypes.CDLL(LIB_PATH)
-    L.rtp_last_error.restype = ctypes.c_char_p
-    L.rtp_abi_version.restype = ctypes.c_int32
-    vp = ctypes.c_void_p
-    L.rtp_create.argtypes = [ctypes.c_int32, ctypes.POINTER(vp)]
-    L.rtp_destroy.argtypes = [vp]
-    L.rtp_destroy.restype = None
-    L.rtp_set_scene.argtypes = [vp, ctypes.POINTER(RtpSceneDesc)]
-    L.rtp_render.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                             ctypes.c_int32, ctypes.c_uint32, f32p, ctypes.POINTER(RtpStats)]
-    L.rtp_render_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
-                                    ctypes.c_int64, vp, vp, ctypes.POINTER(RtpPixelAux), vp,
-                                    ctypes.POINTER(RtpStats)]
-    L.rtp_render_tiles_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
-                                          ctypes.c_int32, vp, vp, ctypes.POINTER(RtpStats)]
-    L.rtp_render_pixels.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, i64p, ctypes.c_int64, f32p,
-                                    ctypes.POINTER(RtpPixelAux), ctypes.POINTER(RtpStats)]
-    L.rtp_normalize.argtypes = [f32p, ctypes.c_int64, ctypes.c_int32]
-    L.rtp_write_pnm.argtypes = [ctypes.c_char_p, f32p, ctypes.c_int32, ctypes.c_int32]
-    L.rtp_cornell_box.argtypes = [ctypes.c_int32, ctypes.POINTER(RtpSceneDesc)]
-    L.rtp_eval_primitive.argtypes = [vp, ctypes.c_int32, vp, vp, ctypes.c_int64]
-    L.rtp_debug_closest_hit.argtypes = [vp, vp, ctypes.c_int64, vp]
-    L.rtp_debug_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]
-    L.rtp_verify_fast_math.argtypes = [vp, ctypes.c_int32, ctypes.c_uint32, ctypes.c_uint32,
-                                       ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32)]
-    d64p = ctypes.POINTER(ctypes.c_double)
-    L.rtp_render_direct.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.POINTER(RtpDirectDesc), f32p, f32p, f32p, f32p, ctypes.POINTER(RtpStats)]
-    L.rtp_render_direct_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.POINTER(RtpDirectDesc), vp, vp, vp, vp, vp,
-                                           ctypes.POINTER(RtpStats)]
-    L.rtp_sample_color_table.argtypes = [d64p, ctypes.c_int32, d64p, ctypes.c_int32, d64p, ctypes.c_int32, f32p]
-    L.rtp_quad_scalars.argtypes = [f32p, ctypes.c_int32, i32p, ctypes.c_int32, f32p]
-    L.rtp_cornell_point_field.argtypes = [ctypes.c_int32, ctypes.POINTER(f32p), ctypes.POINTER(ctypes.c_int32),
-                                          ctypes.POINTER(i32p), ctypes.POINTER(ctypes.c_int32)]
-    L.rtp_write_pnm_depth.argtypes = [ctypes.c_char_p, f32p, ctypes.c_int32, ctypes.c_int32]
-    L.rtp_eval_powf.argtypes = [vp, f32p, ctypes.c_float, f32p, ctypes.c_int64]
-    L.rtp_render_planned_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64,
-                                            ctypes.c_int64, vp, vp, ctypes.c_int32, vp, ctypes.POINTER(RtpPixelAux),
-                                            vp, ctypes.POINTER(RtpStats)]
     # An experiment library named by RTP_LIB_PATH may be built from a revision
-    # before the batched views (tools/build_variant.sh RTP_SRC_REV, the A/B
-    # baseline of tools/views_bench.py): it loads without them, and calling
-    # them raises AttributeError.  The in-tree library must export them.
-    older = bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_render_views_device")
-    skip = ("rtp_render_views_device", "rtp_render_views") if older else ()
-    # (likewise a revision before the resumable render: tools/progressive_bench.py's baseline)
-    no_resume = bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_render_resume_device")
-    if no_resume:
-        skip += ("rtp_render_resume_device", "rtp_render_resume")
-    else:
-        L.rtp_render_resume_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, vp,
-                                               ctypes.POINTER(RtpRenderState), vp, ctypes.POINTER(RtpStats)]
-        L.rtp_render_resume.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32,
-                                        ctypes.c_int32, ctypes.c_int32, i64p, ctypes.c_int64,
-                                        ctypes.POINTER(RtpRenderState), ctypes.POINTER(RtpStats)]
-    if not older:
-        L.rtp_render_views_device.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, vp,
-                                              ctypes.POINTER(RtpPixelAux), vp, ctypes.POINTER(RtpStats)]
-        L.rtp_render_views.argtypes = [vp, ctypes.POINTER(RtpView), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                       ctypes.c_int32, ctypes.c_int32, f32p, ctypes.POINTER(RtpStats)]
-    # (likewise a revision before the denoised previews)
-    if bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_denoise_device"):
-        skip += ("rtp_render_guides_device", "rtp_render_guides", "rtp_resolve_device", "rtp_resolve",
-                 "rtp_denoise_device", "rtp_denoise")
-    else:
-        stp, dpp = ctypes.POINTER(RtpStats), ctypes.POINTER(RtpDenoiseParams)
-        L.rtp_render_guides_device.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32, vp, vp,
-                                               vp, vp, stp]
-        L.rtp_render_guides.argtypes = [vp, ctypes.POINTER(RtpCamera), ctypes.c_int32, ctypes.c_int32, f32p, f32p,
-                                        i32p, stp]
-        L.rtp_resolve_device.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int64, vp, vp, stp]
-        L.rtp_resolve.argtypes = [vp, f32p, f32p, i32p, ctypes.c_int32, ctypes.c_int64, f32p, stp]
-        L.rtp_denoise_device.argtypes = [vp, vp, vp, vp, ctypes.c_int32, ctypes.c_int32, dpp, vp, vp, vp, stp]
-        L.rtp_denoise.argtypes = [vp, f32p, f32p, f32p, ctypes.c_int32, ctypes.c_int32, dpp, f32p, stp]
-    # (likewise a revision before rtp_debug_bounce: the parent build a change is timed against)
-    if bool(os.environ.get("RTP_LIB_PATH")) and not hasattr(L, "rtp_debug_bounce"):
-        skip += ("rtp_debug_bounce",)
-    else:
-        L.rtp_debug_bounce.argtypes = [vp, vp, vp, ctypes.c_int64, vp]
-    L.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
-    L.rtp_get_ff_tables.argtypes = [vp, ctypes.POINTER(RtpFfInfo)]
-    L.rtp_sphere_walk.argtypes = [vp]
-    L.rtp_sphere_walk_oct_mask.argtypes = [vp]
-    for name in EXPORTED_SYMBOLS:
-        if name not in ("rtp_last_error", "rtp_abi_version", "rtp_destroy") + skip:
-            getattr(L, name).restype = ctypes.c_int32
+    # before any of the symbols (tools/build_variant.sh RTP_SRC_REV, the A/B
+    # baselines of the tools/*_bench.py): it loads without them, and calling
+    # one raises AttributeError.  The in-tree library must export them all.
+    missing = []
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            missing.append(name)
+            continue
+        fn.restype, fn.argtypes = restype, argtypes
+    if missing and not os.environ.get("RTP_LIB_PATH"):
+        raise RuntimeError(f"{LIB_PATH} does not export {', '.join(missing)}; rebuild it "
+                           "(raytracingtherestofyourlife_amd/build.py)")
     _lib = L
     return L
 
@@ -224,3 +205,35 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
 def check(status: int) -> None:
     if status != RTP_OK:
         raise RtpError(status, load().rtp_last_error().decode(errors="replace"))
+
+
+# ------------------------------------------------------------ pointers --
+# What ctypes converts by itself once argtypes are declared needs no helper:
+# an int (0 = NULL) or None for a c_void_p argument, an instance for a
+# POINTER(T) argument.  The two conversions it leaves to the caller:
+_POINTEE = {"float32": ctypes.c_float, "float64": ctypes.c_double, "int32": ctypes.c_int32,
+            "uint32": ctypes.c_uint32, "int64": ctypes.c_int64, "uint64": ctypes.c_uint64}
+
+
+def ptr(a):
+    """A numpy array's memory as the pointer type of its dtype (None: NULL).
+    The array is the caller's to keep contiguous and alive across the call."""
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(_POINTEE[a.dtype.name]))
+
+
+def _field(x, ptype):
+    """A typed pointer for a struct field from what a caller holds: a host
+    array (its dtype must be the field's) or a device address (0 or None: NULL)."""
+    if hasattr(x, "ctypes"):
+        return ptr(x)
+    return ctypes.cast(x, ptype) if x else None
+
+
+def pixel_aux(seed, live) -> RtpPixelAux:
+    """rtp_pixel_aux of two optional buffers: host uint32 arrays or device addresses."""
+    return RtpPixelAux(_field(seed, u32p), _field(live, u32p))
+
+
+def render_state(rgba, seed, live=None, m2=None) -> RtpRenderState:
+    """rtp_render_state likewise (rgba, m2: float32; seed, live: uint32)."""
+    return RtpRenderState(_field(rgba, f32p), _field(seed, u32p), _field(live, u32p), _field(m2, f32p))

@@ -18,12 +18,10 @@ mapper render.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
 from . import _lib
-from ._lib import RtpDirectDesc, RtpStats, check
+from ._lib import RtpDirectDesc, check, ptr
 from .mapper import Camera, CanvasRayTracer, CellSet, CornellBox, Device, ErrorBadValue, Field
 
 
@@ -45,10 +43,8 @@ class ColorTable:
     def Sample(self, n: int = 1024) -> np.ndarray:
         """Mapper::SetActiveColorTable: Sample(n) as Vec4ui_8, * (1/255.f)."""
         out = np.zeros((n, 4), dtype=np.float32)
-        d64 = ctypes.POINTER(ctypes.c_double)
-        check(_lib.load().rtp_sample_color_table(
-            self.rgb_points.ctypes.data_as(d64), self.rgb_points.size, self.alpha_points.ctypes.data_as(d64),
-            self.alpha_points.size, self.nan_color.ctypes.data_as(d64), n, out.ctypes.data_as(_lib.f32p)))
+        check(_lib.load().rtp_sample_color_table(ptr(self.rgb_points), self.rgb_points.size, ptr(self.alpha_points),
+                                                 self.alpha_points.size, ptr(self.nan_color), n, ptr(out)))
         return out
 
 
@@ -124,8 +120,7 @@ def quad_scalars(field_values: np.ndarray, quad_cells: np.ndarray) -> np.ndarray
     f = np.ascontiguousarray(field_values, dtype=np.float32)
     c = np.ascontiguousarray(quad_cells, dtype=np.int32)
     out = np.zeros(c.size, dtype=np.float32)
-    check(_lib.load().rtp_quad_scalars(f.ctypes.data_as(_lib.f32p), f.size, c.ctypes.data_as(_lib.i32p), c.size,
-                                       out.ctypes.data_as(_lib.f32p)))
+    check(_lib.load().rtp_quad_scalars(ptr(f), f.size, ptr(c), c.size, ptr(out)))
     return out
 
 
@@ -147,15 +142,11 @@ def render_direct(dev: Device, camera: Camera, nx: int, ny: int, qscalar: np.nda
     d.clip_near, d.clip_far = float(camera.clipping[0]), float(camera.clipping[1])
     d.background[:] = [float(v) for v in background]
     d.composite_background = int(bool(composite))
-    d.quad_scalar = qs.ctypes.data_as(_lib.f32p)
-    d.color_map = cm.ctypes.data_as(_lib.f32p) if cm is not None else None
+    d.quad_scalar = ptr(qs)
+    d.color_map = ptr(cm)
     d.color_map_size = 0 if cm is None else cm.shape[0]
-    st = RtpStats()
-    cam = camera.to_c()
-    ptr = lambda k: outs[k].ctypes.data_as(_lib.f32p) if k in outs else None
-    check(dev._L.rtp_render_direct(dev.handle, ctypes.byref(cam), nx, ny, ctypes.byref(d), ptr("color"),
-                                   ptr("normals"), ptr("albedo"), ptr("depth"), ctypes.byref(st)))
-    outs["stats"] = st
+    outs["stats"] = dev._call("rtp_render_direct", camera.to_c(), nx, ny, d,
+                              *(ptr(outs.get(k)) for k in ("color", "normals", "albedo", "depth")))
     return outs
 
 
@@ -282,4 +273,4 @@ def runDirect(nx: int, ny: int, cam: Camera, cb: CornellBox, device: int | Devic
 def save_depth_pnm(path: str, depth: np.ndarray, nx: int, ny: int) -> None:
     """save<vtkm::Float32> (main.cc:346-359)."""
     a = np.ascontiguousarray(depth, dtype=np.float32)
-    check(_lib.load().rtp_write_pnm_depth(path.encode(), a.ctypes.data_as(_lib.f32p), nx, ny))
+    check(_lib.load().rtp_write_pnm_depth(path.encode(), ptr(a), nx, ny))

@@ -33,6 +33,142 @@ def test_library_exports_every_declared_symbol():
     assert set(names) == set(rtp._lib.EXPORTED_SYMBOLS)
 
 
+def _prototypes():
+    """include/rtp.h's functions: name -> (return type, [argument declarations])."""
+    src = open(os.path.join(ROOT, "include", "rtp.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(rtp_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
+        args = [a.strip() for a in args.split(",")]
+        protos[name] = (" ".join(ret.split()), [] if args == ["void"] else args)
+    return protos
+
+
+def _c_class(decl: str):
+    """(base type, pointer depth) of a C argument declaration `type name` or `type name[n]`."""
+    ctype, array = re.fullmatch(r"(.*?)\b\w+\s*(\[\d*\])?", decl).groups()
+    words = [w for w in ctype.replace("*", " ").split() if w != "const"]
+    return words[0], ctype.count("*") + (1 if array else 0)
+
+
+def _agrees(ct, base: str, depth: int) -> bool:
+    """The ctypes type `ct` against a C declaration of `base` with `depth` stars."""
+    from raytracingtherestofyourlife_amd import _lib
+
+    scalars = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+               "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
+    structs = {"rtp_camera": _lib.RtpCamera, "rtp_view": _lib.RtpView, "rtp_scene_desc": _lib.RtpSceneDesc,
+               "rtp_stats": _lib.RtpStats, "rtp_pixel_aux": _lib.RtpPixelAux, "rtp_render_state": _lib.RtpRenderState,
+               "rtp_direct_desc": _lib.RtpDirectDesc, "rtp_denoise_params": _lib.RtpDenoiseParams,
+               "rtp_ff_info": _lib.RtpFfInfo}
+    if depth == 0:
+        return base in ("int32_t", "uint32_t", "int64_t", "float") and ct is scalars[base]
+    if ct is ctypes.c_void_p:
+        return True
+    if ct is ctypes.c_char_p:
+        return base == "char" and depth == 1
+    if isinstance(ct, type) and issubclass(ct, ctypes._Pointer):
+        if depth > 1:
+            return _agrees(ct._type_, base, depth - 1)
+        # the pointee the header names; rtp_context and void have no mirror and must be c_void_p
+        return ct._type_ is {**scalars, **structs}.get(base)
+    return False
+
+
+def test_signature_table_matches_the_header():
+    """Every row of _lib.SIGNATURES against its prototype: argument count,
+    each argument's class (exact scalar; pointer kind and pointee), return class."""
+    from raytracingtherestofyourlife_amd import _lib
+
+    protos = _prototypes()
+    assert set(protos) == set(_lib.SIGNATURES) and len(protos) == 39
+    assert list(protos) == list(_lib.SIGNATURES), "the table is in the header's order"
+    returns = {"rtp_status": ctypes.c_int32, "int32_t": ctypes.c_int32, "const char*": ctypes.c_char_p, "void": None}
+    bad = []
+    for name, (ret, args) in protos.items():
+        restype, argtypes = _lib.SIGNATURES[name]
+        if restype is not returns[ret]:
+            bad.append(f"{name}: returns {ret}, table {restype}")
+        if len(argtypes) != len(args):
+            bad.append(f"{name}: {len(args)} arguments, table {len(argtypes)}")
+            continue
+        bad += [f"{name}: argument {k} `{decl}`, table {ct}" for k, (decl, ct) in enumerate(zip(args, argtypes))
+                if not _agrees(ct, *_c_class(decl))]
+    assert not bad, "\n".join(bad)
+    # and load() applied the table
+    L = _lib.load()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+
+
+def test_load_missing_symbol_rule(tmp_path, monkeypatch):
+    """A library named by RTP_LIB_PATH may lack symbols (calling one raises
+    AttributeError); the in-tree library must export them all."""
+    import raytracingtherestofyourlife_amd._lib as L
+
+    src, stub = tmp_path / "stub.c", str(tmp_path / "libstub.so")
+    src.write_text('const char* rtp_last_error(void) { return ""; }\nint rtp_abi_version(void) { return 3; }\n')
+    subprocess.run([os.environ.get("CC", "cc"), "-shared", "-fPIC", str(src), "-o", stub], check=True,
+                   capture_output=True)
+    monkeypatch.setattr(L, "LIB_PATH", stub)
+    monkeypatch.setattr(L, "_lib", None)
+    monkeypatch.setenv("RTP_LIB_PATH", stub)
+    lib = L.load(build_if_missing=False)
+    assert lib.rtp_abi_version() == 3
+    with pytest.raises(AttributeError):
+        lib.rtp_render_views
+    monkeypatch.setattr(L, "_lib", None)
+    monkeypatch.delenv("RTP_LIB_PATH")
+    with pytest.raises(RuntimeError, match="rtp_render_views"):
+        L.load(build_if_missing=False)
+    assert L._lib is None
+
+
+def test_debug_counter_names_cover_the_enum():
+    from raytracingtherestofyourlife_amd import _lib
+
+    src = open(os.path.join(os.path.dirname(_lib.__file__), "csrc", "rtp_layout.hpp")).read()
+    body = re.search(r"enum DbgCounter \{(.*?)\bkDbgCounters\b", src, flags=re.S).group(1)
+    enumerators = re.findall(r"\bkDbg\w+", re.sub(r"//[^\n]*", "", body))
+    assert len(enumerators) == len(set(enumerators)) == len(_lib.DEBUG_COUNTERS) - 1 == _lib.N_DBG_COUNTERS
+    assert _lib.DEBUG_COUNTERS[-1] == "max_wave_cycles"
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+def test_scene_desc_of_cornell_arrays_equals_the_librarys(variant):
+    """CornellBox(v).buildDataSet()'s arrays through the package's one scene
+    hand-over and device.scene_desc give rtp_cornell_box(v)'s own descriptor."""
+    import raytracingtherestofyourlife_amd as rtp
+    from raytracingtherestofyourlife_amd import _lib, device, mapper
+
+    class Recorder:
+        def set_scene(self, *args):
+            self.desc, self.arrays = device.scene_desc(*args)
+
+    cb = rtp.CornellBox(variant)
+    cb.buildDataSet()
+    rec = Recorder()
+    mapper._set_cornell_scene(rec, cb)
+    got, want = rec.desc, _lib.RtpSceneDesc()
+    _lib.check(rtp.load().rtp_cornell_box(variant, want))
+    counts = ("n_points", "n_quads", "n_spheres", "n_mat", "n_tex_type", "n_tex")
+    assert [getattr(got, k) for k in counts] == [getattr(want, k) for k in counts]
+    assert want.n_quads > 0 and want.n_spheres > 0
+    sizes = dict(points=3 * want.n_points, quad_points=4 * want.n_quads, quad_mat=want.n_quads,
+                 quad_tex=want.n_quads, sphere_point=want.n_spheres, sphere_radius=want.n_spheres,
+                 sphere_mat=want.n_spheres, sphere_tex=want.n_spheres, mat_type=want.n_mat,
+                 tex_type=want.n_tex_type, tex_rgb=3 * want.n_tex)
+    pointers = [f for f, t in _lib.RtpSceneDesc._fields_ if issubclass(t, ctypes._Pointer)]
+    assert sorted(pointers) == sorted(sizes)
+    for f, n in sizes.items():
+        a = np.ctypeslib.as_array(getattr(got, f), shape=(n,))
+        b = np.ctypeslib.as_array(getattr(want, f), shape=(n,))
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), f
+    assert list(got.light_quad_points) == list(want.light_quad_points)
+    assert got.light_sphere_point == want.light_sphere_point
+    assert np.float32(got.ior).tobytes() == np.float32(want.ior).tobytes()
+
+
 def test_abi_version():
     import raytracingtherestofyourlife_amd as rtp
 

@@ -73,6 +73,7 @@ def test_stats_instance(device, tables, instance, monkeypatch):
         monkeypatch.setenv("RTP_DEBUG_STATS", "1")
         got = _render(device, instance == "planned")
         c = device.debug_counters()
+        records = device.debug_wave_records() if instance == "plain" else None
         monkeypatch.delenv("RTP_DEBUG_STATS")
     finally:
         device.set_cornell_box(0)
@@ -91,3 +92,8 @@ def test_stats_instance(device, tables, instance, monkeypatch):
     assert 0 <= ended <= N * SPP and c["ffrad_lanes"] == c["light_lanes"]
     if tables == "off":
         assert c["dead_lanes"] == N * SPP * DEPTH - live + ended
+    if records is not None:  # the raw per-wave records are what debug_counters() sums
+        names = device.DEBUG_COUNTERS[:-1]
+        assert records.dtype == np.uint64 and records.shape == (c["waves"], len(names))
+        assert records.sum(axis=0, dtype=np.uint64).tolist() == [c[k] for k in names]
+        assert int(records[:, names.index("cycles_total")].max()) == c["max_wave_cycles"]

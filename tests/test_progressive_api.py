@@ -28,15 +28,29 @@ def test_library_exports_resume_symbols():
 
 
 def test_render_state_layout_matches_the_header(tmp_path):
+    """rtp_render_state and every other struct of include/rtp.h that _lib.py
+    mirrors: size, and each field's name and offset in declaration order."""
+    from raytracingtherestofyourlife_amd import _lib
     from raytracingtherestofyourlife_amd._lib import RtpRenderState
 
     exe = str(tmp_path / "state_layout_check")
     subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-I", os.path.join(ROOT, "include"),
                     os.path.join(ROOT, "tests", "cpp", "state_layout_check.cpp"), "-o", exe], check=True,
                    capture_output=True)
-    size, *offsets = (int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split())
-    assert ctypes.sizeof(RtpRenderState) == size
-    assert [getattr(RtpRenderState, f).offset for f in ("rgba", "seed", "live_bounces", "m2")] == offsets
+    mirrors = dict(rtp_camera=_lib.RtpCamera, rtp_view=_lib.RtpView, rtp_scene_desc=_lib.RtpSceneDesc,
+                   rtp_stats=_lib.RtpStats, rtp_pixel_aux=_lib.RtpPixelAux, rtp_render_state=RtpRenderState,
+                   rtp_direct_desc=_lib.RtpDirectDesc, rtp_denoise_params=_lib.RtpDenoiseParams,
+                   rtp_ff_info=_lib.RtpFfInfo)
+    seen = []
+    for line in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines():
+        if not line:
+            continue
+        name, size, *fields = line.split()
+        mirror = mirrors[name]
+        assert ctypes.sizeof(mirror) == int(size), name
+        assert [f"{f}={getattr(mirror, f).offset}" for f, _ in mirror._fields_] == fields, name
+        seen.append(name)
+    assert seen == list(mirrors)
     assert [f for f, _ in RtpRenderState._fields_] == ["rgba", "seed", "live_bounces", "m2"]
 
 

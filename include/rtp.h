@@ -499,6 +499,16 @@ rtp_status rtp_debug_closest_hit(rtp_context* ctx, const float* rays, int64_t n,
  * attenuation is not finite. */
 rtp_status rtp_debug_bounce(rtp_context* ctx, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out);
 
+/* Diagnostics: the path kernel's camera ray (Camera::RayGen, two draws) for
+ * n rows of (pixel index, RNG state) on an nx x ny canvas under `camera`.
+ * out (host, 12 + 5 n u32): the twelve camera constants the host derived for
+ * the launch (eye, nlook, delta_x, delta_y: float bits), then per row the
+ * direction (float bits), the RNG state after the two draws, and the pixel
+ * index j * nx + i of the (i, j) the kernel split the row's index into.
+ * Needs a scene, like a render; pixels must lie in [0, nx * ny). */
+rtp_status rtp_debug_raygen(rtp_context* ctx, const rtp_camera* camera, int32_t nx, int32_t ny, const int64_t* pixels,
+                            const uint32_t* seeds, int64_t n, uint32_t* out);
+
 /* Diagnostics: how the current scene's spheres are searched by a render
  * (rtp_render*, without RTP_DEBUG_STATS or a wave plan): 0 every sphere in
  * order (fewer than 9 spheres), 1 the threaded sphere BVH in global memory,

@@ -234,6 +234,56 @@ def bounce(scene: Scene, rays, seeds) -> np.ndarray:
     return out
 
 
+def _frame_fns():
+    L = _stage_fns()
+    if not hasattr(L, "_frames_ready"):
+        u32p, scp, f32p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(Scene), ctypes.POINTER(ctypes.c_float)
+        L.rtpo_stage_raygen.argtypes = [u32p, ctypes.c_int64, u32p]
+        L.rtpo_stage_raygen.restype = None
+        L.rtpo_stage_backward.argtypes = [u32p, ctypes.c_int64, ctypes.c_int32, u32p]
+        L.rtpo_stage_backward.restype = None
+        L.rtpo_render_soa_states.argtypes = [scp, f32p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             ctypes.c_uint32, f32p, u32p, u32p, u32p]
+        L.rtpo_render_soa_states.restype = ctypes.c_int32
+        L._frames_ready = True
+    return L
+
+
+def stage_raygen(cases) -> np.ndarray:
+    """rtpo_stage_raygen: (n, 14) words (position, look-at, up, fov, nx, ny, work index, seed) -> (n, 5)."""
+    cases = np.ascontiguousarray(cases, dtype=np.uint32)
+    assert cases.ndim == 2 and cases.shape[1] == 14, cases.shape
+    out = np.zeros((len(cases), 5), dtype=np.uint32)
+    _frame_fns().rtpo_stage_raygen(_up(cases), len(cases), _up(out))
+    return out
+
+
+def stage_backward(cases) -> np.ndarray:
+    """rtpo_stage_backward: (n, 2 + 8*S*D) words, each row starting with its D and S -> (n, 4)."""
+    cases = np.ascontiguousarray(cases, dtype=np.uint32)
+    d, s = int(cases[0, 0]), int(cases[0, 1])
+    assert cases.shape[1] == 2 + 8 * s * d and (cases[:, 0] == d).all() and (cases[:, 1] == s).all()
+    out = np.zeros((len(cases), 4), dtype=np.uint32)
+    _frame_fns().rtpo_stage_backward(_up(cases), len(cases), cases.shape[1], _up(out))
+    return out
+
+
+def render_soa_states(scene: Scene, cam: np.ndarray, nx: int, ny: int, spp: int, depth: int, seed_base: int = 0):
+    """rtpo_render_soa over the whole canvas with every ray's state after every depth of every sample:
+    (rgba[n,4], seeds[n], live[n], states[spp, depth, n, 37] uint32)."""
+    n = nx * ny
+    rgba = np.zeros((n, 4), dtype=np.float32)
+    seeds = np.zeros(n, dtype=np.uint32)
+    live = np.zeros(n, dtype=np.uint32)
+    states = np.zeros((spp, depth, n, BOUNCE_WORDS), dtype=np.uint32)
+    cam = np.ascontiguousarray(cam, dtype=np.float32)
+    rc = _frame_fns().rtpo_render_soa_states(ctypes.byref(scene), _fp(cam), nx, ny, spp, depth, seed_base, _fp(rgba),
+                                             _up(seeds), _up(live), _up(states))
+    if rc != 0:
+        raise ValueError("rtpo_render_soa_states: invalid arguments")
+    return rgba, seeds, live, states
+
+
 # ------------------------------------------------------------ -direct mode ---
 class DirectCam(ctypes.Structure):
     """Mirror of rtpo_direct_cam."""

@@ -697,6 +697,17 @@ static int scene_hit(const rtpo_scene* sc, v3 o, v3 d, hitrec* rec, int* hm, int
   return hit;
 }
 
+/* The backward product of one sample, MapperPathTracer.cxx:328-348: sumtotl = E[D-1] + 0, then for
+ * d = D-2 .. 0: sumtotl = A[d] * sumtotl; sumtotl = E[d] + sumtotl. */
+static inline v3 backward_product(const v3* A, const v3* E, int32_t depth) {
+  v3 sum = add(E[depth - 1], mk(0, 0, 0));
+  for (int d = depth - 2; d >= 0; d--) {
+    sum = mk(A[d].x * sum.x, A[d].y * sum.y, A[d].z * sum.z);
+    sum = add(E[d], sum);
+  }
+  return sum;
+}
+
 /* One pixel, S samples x D depths, in the stage order of
  * MapperPathTracer.cxx:278-354. A/E hold attenuation/emitted per depth. */
 static void trace_pixel(const rtpo_scene* sc, const lights* L, const float cam[12], int32_t nx, int32_t ny,
@@ -791,11 +802,7 @@ static void trace_pixel(const rtpo_scene* sc, const lights* L, const float cam[1
       dir = out_d;
     }
     /* backward radiance, MapperPathTracer.cxx:328-348, then cols += s (:350) */
-    v3 sum = add(E[depth - 1], mk(0, 0, 0));
-    for (int d = depth - 2; d >= 0; d--) {
-      sum = mk(A[d].x * sum.x, A[d].y * sum.y, A[d].z * sum.z);
-      sum = add(E[d], sum);
-    }
+    v3 sum = backward_product(A, E, depth);
     col[0] = col[0] + sum.x;
     col[1] = col[1] + sum.y;
     col[2] = col[2] + sum.z;
@@ -885,11 +892,12 @@ static inline uint32_t fbits(float f) {
   memcpy(&u, &f, 4);
   return u;
 }
-static void soa_record(const soa_t* R, int64_t n, int dep, int c, uint32_t* rec) {
+/* ray i at word rec[(i * stride + c) * RTPO_BOUNCE_WORDS] */
+static void soa_record_strided(const soa_t* R, int64_t n, int dep, int64_t stride, int64_t c, uint32_t* rec) {
   if (!rec) return;
   const int64_t off = (int64_t)dep * n;
   for (int64_t i = 0; i < n; i++) {
-    uint32_t* w = rec + ((int64_t)i * RTPO_BOUNCE_PASSES + c) * RTPO_BOUNCE_WORDS;
+    uint32_t* w = rec + ((int64_t)i * stride + c) * RTPO_BOUNCE_WORDS;
     const float f[] = {R->ht[i],  R->hnx[i], R->hny[i], R->hnz[i], R->hpx[i], R->hpy[i], R->hpz[i]};
     const float g[] = {R->sox[i], R->soy[i], R->soz[i], R->sdx[i], R->sdy[i], R->sdz[i], R->sax[i], R->say[i], R->saz[i]};
     const float h[] = {R->gx[i], R->gy[i], R->gz[i], R->sum[i], R->Ex[off + i], R->Ey[off + i], R->Ez[off + i],
@@ -905,6 +913,9 @@ static void soa_record(const soa_t* R, int64_t n, int dep, int c, uint32_t* rec)
     for (int j = 0; j < 16; j++) w[k++] = fbits(h[j]);
     w[k++] = R->seeds[i];
   }
+}
+static void soa_record(const soa_t* R, int64_t n, int dep, int c, uint32_t* rec) {
+  soa_record_strided(R, n, dep, RTPO_BOUNCE_PASSES, c, rec);
 }
 
 /* One depth of RenderCellsImpl (MapperPathTracer.cxx:286-301) over all n rays: the resets and thirteen
@@ -1133,9 +1144,9 @@ static void soa_depth(const rtpo_scene* sc, const lights* Lp, const soa_t* Rp, i
   soa_record(&R, n, dep, 12, rec);
 }
 
-int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
-                        int32_t depth, uint32_t seed_base, int32_t row_begin, int32_t row_end, float* out_rgba,
-                        uint32_t* out_seed, uint32_t* out_live, int32_t nthreads) {
+static int32_t render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
+                          int32_t depth, uint32_t seed_base, int32_t row_begin, int32_t row_end, float* out_rgba,
+                          uint32_t* out_seed, uint32_t* out_live, int32_t nthreads, uint32_t* states) {
   if (depth < 1 || spp < 0 || row_begin < 0 || row_end > ny || row_begin >= row_end) return -1;
 #ifdef _OPENMP
   if (nthreads <= 0) nthreads = omp_get_max_threads();
@@ -1159,7 +1170,10 @@ int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, i
       R.ox[i] = cam[0], R.oy[i] = cam[1], R.oz[i] = cam[2];
       R.status[i] = 1u << 3;
     }
-    for (int dep = 0; dep < depth; dep++) soa_depth(sc, &L, &R, n, dep, nthreads, RTPO_PASS_ALL, NULL);
+    for (int dep = 0; dep < depth; dep++) {
+      soa_depth(sc, &L, &R, n, dep, nthreads, RTPO_PASS_ALL, NULL);
+      if (states) soa_record_strided(&R, n, dep, 1, 0, states + ((int64_t)s * depth + dep) * n * RTPO_BOUNCE_WORDS);
+    }
     /* backward SliceTransform passes (MapperPathTracer.cxx:328-348) */
     {
       const int64_t off = (int64_t)(depth - 1) * n;
@@ -1200,6 +1214,19 @@ int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, i
   soa_free(&R);
   free(cols);
   return 0;
+}
+
+int32_t rtpo_render_soa(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
+                        int32_t depth, uint32_t seed_base, int32_t row_begin, int32_t row_end, float* out_rgba,
+                        uint32_t* out_seed, uint32_t* out_live, int32_t nthreads) {
+  return render_soa(sc, cam, nx, ny, spp, depth, seed_base, row_begin, row_end, out_rgba, out_seed, out_live, nthreads,
+                    NULL);
+}
+
+int32_t rtpo_render_soa_states(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
+                               int32_t depth, uint32_t seed_base, float* out_rgba, uint32_t* out_seed,
+                               uint32_t* out_live, uint32_t* states) {
+  return render_soa(sc, cam, nx, ny, spp, depth, seed_base, 0, ny, out_rgba, out_seed, out_live, 1, states);
 }
 
 /* One depth of the stage-structured variant from given rays (rtp_oracle.h) */
@@ -1469,6 +1496,48 @@ void rtpo_stage_collect(const rtpo_scene* sc, const uint32_t* in, int64_t n, uin
     st3(o + 1, R.Ex, R.Ey, R.Ez, i), st3(o + 4, R.Ax, R.Ay, R.Az, i);
   }
   soa_free(&S.R);
+}
+
+
+/* Ray generation: rtpo_camera_setup and the raygen() every render calls.  Row: position, look-at, up, fov,
+ * nx, ny, work index, seed -> direction, seed after, the pixel the oracle attributes the ray to (the work
+ * index itself: trace_pixel and rtpo_render_soa sum ray idx into pixel idx). */
+void rtpo_stage_raygen(const uint32_t* in, int64_t n, uint32_t* out) {
+  for (int64_t c = 0; c < n; c++) {
+    const word* w = (const word*)in + 14 * c;
+    word* o = (word*)out + 5 * c;
+    float pos[3] = {w[0].f, w[1].f, w[2].f}, at[3] = {w[3].f, w[4].f, w[5].f}, up[3] = {w[6].f, w[7].f, w[8].f};
+    float cam[12];
+    rtpo_camera_setup(pos, at, up, w[9].f, w[10].i, w[11].i, cam);
+    uint32_t seed = w[13].u;
+    stw(o, raygen(cam, w[10].i, w[11].i, w[12].i, &seed));
+    o[3].u = seed;
+    o[4].i = w[12].i;
+  }
+}
+
+/* The backward product and the canvas sum of trace_pixel.  Row: D, S, then per sample and depth emitted
+ * (rgb, alpha) and attenuation (rgb, alpha); kin = 2 + 8*S*D -> the canvas rgb and alpha (0: the oracle
+ * keeps no alpha lane). */
+void rtpo_stage_backward(const uint32_t* in, int64_t n, int32_t kin, uint32_t* out) {
+  for (int64_t c = 0; c < n; c++) {
+    const word* w = (const word*)in + (int64_t)kin * c;
+    word* o = (word*)out + 4 * c;
+    const int32_t D = w[0].i, S = w[1].i;
+    v3* A = (v3*)malloc(sizeof(v3) * D);
+    v3* E = (v3*)malloc(sizeof(v3) * D);
+    float col[3] = {0, 0, 0};
+    w += 2;
+    for (int s = 0; s < S; s++) {
+      for (int d = 0; d < D; d++, w += 8) E[d] = ldw(w), A[d] = ldw(w + 4);
+      v3 sum = backward_product(A, E, D);
+      col[0] = col[0] + sum.x;
+      col[1] = col[1] + sum.y;
+      col[2] = col[2] + sum.z;
+    }
+    o[0].f = col[0], o[1].f = col[1], o[2].f = col[2], o[3].f = 0.0f;
+    free(A), free(E);
+  }
 }
 
 /* NormalizeFunctor, main.cc:253-287 (alpha is normalised too; rgb de-NaN'd) */

@@ -7,22 +7,30 @@
  * by tests/ (as the parity checker), by __graft_entry__.smoke() (checker) and
  * by bench.py's cpu_baseline leg (timed CPU baseline, kind "port").
  *
- * Parity status: pinned to the reference's own worklets, stage by stage.  The
- * whole reference cannot be compiled here (it needs VTK-m, absent, see
- * SURVEY.md 8c), but its header-only worklets (PdfWorklet.h, EmitWorklet.h,
- * ScatterWorklet.h, SurfaceWorklets.h, Surface.h, onb.h, wangXor.h, vec3.h)
- * compile unchanged over tests/cpp/vtkm_min/ and are executed by
+ * Parity status: pinned to the reference's own code, stage by stage and as
+ * whole small frames.  The whole reference cannot be compiled here (it needs
+ * VTK-m, absent), but its header-only worklets
+ * (PdfWorklet.h, EmitWorklet.h, ScatterWorklet.h, SurfaceWorklets.h,
+ * Surface.h, onb.h, wangXor.h, vec3.h), PathAlgorithms.h, and the classes
+ * Camera::RayGen and details::WangInit cut out of their .cxx files at build
+ * time compile unchanged over tests/cpp/vtkm_min/ and are executed by
  * tests/cpp/ref_stage_driver.cpp; their recorded results
- * (tests/golden/ref_stages.npz) are what tests/test_ref_stages.py holds the
- * rtpo_stage_* exports and rtpo_bounce below to, bit for bit.
+ * (tests/golden/ref_stages.npz, ref_frames.npz) are what
+ * tests/test_ref_stages.py holds the rtpo_stage_* exports, rtpo_bounce,
+ * rtpo_camera_setup, rtpo_render_pixels and rtpo_render_soa below to, bit
+ * for bit.
  *   Pinned: every arithmetic expression of those worklets (RNG, which, onb,
  *   quad and sphere hit, the three materials, the dielectric's scatter, the
  *   three generators, both light pdfs, PDFCosineWorklet, CollectIntersectt-
- *   Worklet), each alone and in the order of one depth of RenderCellsImpl.
- *   Still restated only: the VTK-m helpers (as tests/cpp/vtkm_min/ states
- *   them), LinearBVH leaf order, the per-depth glue of RenderCellsImpl, the
- *   backward product, ray generation (Camera.cxx; Worklets.h's RayGen is a
- *   different text), the scene builder and everything of -direct mode.
+ *   Worklet), each alone and in the order of one depth of RenderCellsImpl;
+ *   the camera constants and ray generation; the backward product and the
+ *   canvas sum; the sample and depth loop with every array kept from depth
+ *   to depth and from sample to sample (rgb, final seeds, live counts, and
+ *   every ray's state after every depth).
+ *   Still restated only: the VTK-m helpers and CopyIf (as
+ *   tests/cpp/vtkm_min/ states them), LinearBVH leaf order, libm's tanf, the
+ *   zero content of buffers the reference reads before it writes them, the
+ *   scene builder and everything of -direct mode.
  * Each assumption is listed in DESIGN.md section 2, "Oracle assumptions".
  * Further pins: known-answer tests probed on this host (RNG, glibc sinf/cosf
  * bit-exactness) and the two internal variants (scalar per-pixel and
@@ -182,6 +190,17 @@ void rtpo_stage_generator(const rtpo_scene* sc, const uint32_t* in, int64_t n, u
 void rtpo_stage_light_pdf(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
 void rtpo_stage_scatter(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out); /* PDFCosineWorklet */
 void rtpo_stage_collect(const rtpo_scene* sc, const uint32_t* in, int64_t n, uint32_t* out);
+
+void rtpo_stage_raygen(const uint32_t* in, int64_t n, uint32_t* out);   /* rtpo_camera_setup + raygen() */
+/* rows of kin = 2 + 8*S*D words, each starting with its D and S */
+void rtpo_stage_backward(const uint32_t* in, int64_t n, int32_t kin, uint32_t* out);
+
+/* rtpo_render_soa of the whole canvas on one thread, which also stores every ray's state (the
+ * RTPO_BOUNCE_WORDS words of rtpo_bounce, emitted and attenuation being those of the depth's own plane)
+ * after every depth of every sample: states[((s*depth + d)*nx*ny + i)*RTPO_BOUNCE_WORDS ..]. */
+int32_t rtpo_render_soa_states(const rtpo_scene* sc, const float cam[12], int32_t nx, int32_t ny, int32_t spp,
+                               int32_t depth, uint32_t seed_base, float* out_rgba, uint32_t* out_seed,
+                               uint32_t* out_live, uint32_t* states);
 
 /* One depth (depth 0) of the stage-structured variant for n rays given as
  * rays[6*i..] = origin, direction and seeds[i], all alive (Status = 8) over

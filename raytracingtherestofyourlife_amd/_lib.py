@@ -141,6 +141,7 @@ def _signatures() -> dict:
         "rtp_debug_counters": (i32, [vp, u64p, i32]),
         "rtp_debug_closest_hit": (st, [vp, vp, i64, vp]),
         "rtp_debug_bounce": (st, [vp, vp, vp, i64, vp]),
+        "rtp_debug_raygen": (st, [vp, cam, i32, i32, i64p, P(u32), i64, P(u32)]),
         "rtp_sphere_walk": (i32, [vp]),
         "rtp_sphere_walk_oct_mask": (i32, [vp]),
         "rtp_verify_fast_math": (st, [vp, i32, u32, u32, u64p, P(u32)]),

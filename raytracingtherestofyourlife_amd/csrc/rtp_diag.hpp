@@ -185,4 +185,24 @@ __global__ void rtp_verify_fast_math_kernel(int kind, uint32_t lo, uint64_t coun
   }
 }
 
+// One camera_ray() -- the render kernels' own, two draws -- per host row of
+// (pixel index, seed), one lane per row, the pixel split into (i, j) as the
+// render kernels split it.  out[5 r ..] = the direction, the seed after the
+// draws, j * nx + i.
+__global__ void __launch_bounds__(256) rtp_eval_raygen_kernel(DevCamera cam, int nx, int ny,
+                                                              const int64_t* __restrict__ pixels,
+                                                              const uint32_t* __restrict__ seeds, uint32_t* out,
+                                                              int64_t n) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  const int64_t pix = pixels[r];
+  const int pi = (int32_t)pix % nx, pj = (int32_t)pix / nx;
+  uint32_t seed = seeds[r];
+  const f3 d = camera_ray(cam, pi, pj, nx, ny, seed);
+  uint32_t* w = out + 5 * r;
+  w[0] = __float_as_uint(d.x), w[1] = __float_as_uint(d.y), w[2] = __float_as_uint(d.z);
+  w[3] = seed;
+  w[4] = (uint32_t)(pj * nx + pi);
+}
+
 }  // namespace rtp

@@ -43,6 +43,8 @@ extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const 
                                               int64_t n, int bvh, hipStream_t stream);
 extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const float* rays, const uint32_t* seeds,
                                              uint32_t* out, int64_t n, int bvh, hipStream_t stream);
+extern "C" hipError_t rtp_launch_eval_raygen(const rtp::DevCamera* cam, int nx, int ny, const int64_t* pixels,
+                                             const uint32_t* seeds, uint32_t* out, int64_t n, hipStream_t stream);
 extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
                                         hipStream_t stream);
 extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
@@ -1679,6 +1681,35 @@ rtp_status rtp_debug_bounce(rtp_context* c, const float* rays, const uint32_t* s
   HIP_TRY_AS("rtp_debug_bounce", b.get(&dout, (size_t)n * 60));
   HIP_TRY_AS("rtp_debug_bounce", rtp_launch_eval_bounce(c->d_scene, din, dseed, dout, n, c->use_bvh ? 1 : 0, nullptr));
   HIP_TRY_AS("rtp_debug_bounce", DevBufs::back(out, dout, (size_t)n * 60));
+  return RTP_OK;
+}
+
+// Diagnostics: the render kernels' camera_ray for host rows of (pixel, seed)
+// under the DevCamera a render of this camera and canvas would launch with
+// (rtp_eval_raygen_kernel; 12 u32 of camera constants, then 5 u32 per row).
+rtp_status rtp_debug_raygen(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, const int64_t* pixels,
+                            const uint32_t* seeds, int64_t n, uint32_t* out) {
+  if (!c || !cam || !out || n < 0 || (n > 0 && (!pixels || !seeds)))
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_raygen: bad arguments");
+  RTP_TRY(check_canvas_camera(c, cam, nx, ny, "rtp_debug_raygen"));
+  for (int64_t i = 0; i < n; i++)
+    if (pixels[i] < 0 || pixels[i] >= (int64_t)nx * ny)
+      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_raygen: pixel outside the canvas");
+  rtp::DevCamera dc;
+  camera_setup(cam, nx, ny, &dc);
+  static_assert(sizeof(dc) == 48, "eye, nlook, delta_x, delta_y");
+  std::memcpy(out, &dc, sizeof(dc));
+  if (n == 0) return RTP_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  DevBufs b;
+  int64_t* dpix = nullptr;
+  uint32_t* dseed = nullptr;
+  uint32_t* dout = nullptr;
+  HIP_TRY_AS("rtp_debug_raygen", b.get(&dpix, (size_t)n * 8, pixels));
+  HIP_TRY_AS("rtp_debug_raygen", b.get(&dseed, (size_t)n * 4, seeds));
+  HIP_TRY_AS("rtp_debug_raygen", b.get(&dout, (size_t)n * 20));
+  HIP_TRY_AS("rtp_debug_raygen", rtp_launch_eval_raygen(&dc, nx, ny, dpix, dseed, dout, n, nullptr));
+  HIP_TRY_AS("rtp_debug_raygen", DevBufs::back(out + 12, dout, (size_t)n * 20));
   return RTP_OK;
 }
 

@@ -267,6 +267,13 @@ extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const f
   else hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<false>, g, b, 0, stream, scene, rays, seeds, out, n);
   return hipGetLastError();
 }
+extern "C" hipError_t rtp_launch_eval_raygen(const rtp::DevCamera* cam, int nx, int ny, const int64_t* pixels,
+                                             const uint32_t* seeds, uint32_t* out, int64_t n, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const dim3 g((unsigned)((n + 255) / 256)), b(256);
+  hipLaunchKernelGGL(rtp::rtp_eval_raygen_kernel, g, b, 0, stream, *cam, nx, ny, pixels, seeds, out, n);
+  return hipGetLastError();
+}
 extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
                                         hipStream_t stream) {
   if (p->npix <= 0) return hipSuccess;

@@ -320,6 +320,19 @@ class Device:
         check(self._L.rtp_debug_closest_hit(self.handle, ptr(a), a.shape[0], ptr(out)))
         return out
 
+    def debug_raygen(self, camera: Camera, nx: int, ny: int, pixels, seeds):
+        """The path kernel's camera ray for rows of (pixel index, RNG state):
+        (the 12 camera constants the host derived for the launch as float32
+        -- eye, nlook, delta_x, delta_y --, and (n, 5) uint32: the direction
+        (float bits), the RNG state after the two draws, the pixel index)."""
+        ids = np.ascontiguousarray(pixels, dtype=np.int64).reshape(-1)
+        s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if s.shape[0] != ids.shape[0]:
+            raise ValueError("debug_raygen: one seed per pixel")
+        out = np.zeros(12 + 5 * ids.shape[0], dtype=np.uint32)
+        check(self._L.rtp_debug_raygen(self.handle, camera.to_c(), nx, ny, ptr(ids), ptr(s), ids.shape[0], ptr(out)))
+        return out[:12].view(np.float32).copy(), out[12:].reshape(-1, 5).copy()
+
     def debug_bounce(self, rays: np.ndarray, seeds: np.ndarray) -> np.ndarray:
         """(n, 6) float32 rays (o, d) and (n,) uint32 RNG states -> (n, 15)
         uint32, one depth of the path kernel's bounce: result (0 goes on, 1

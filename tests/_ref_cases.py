@@ -779,3 +779,326 @@ def reference_closest_hits(sc, rays, exe: str = REF_STAGES) -> np.ndarray:
     hs = np.isfinite(ts) & (ts < np.where(hq, tq, FLT_MAX))
     out[hs] = np.stack([fbits(ts[hs]), np.ones(hs.sum(), dtype=U), isph[hs].astype(U)], 1)
     return out
+
+
+# ------------------------------------------- ray generation, the backward product, whole frames --
+# tests/golden/ref_frames.npz: what the reference's own Camera::RayGen (pathtracing/Camera.cxx), details::WangInit
+# (MapperPathTracer.cxx), BinarySliceTransformIdxKernel (PathAlgorithms.h) and the whole sample and depth loop of
+# RenderCellsImpl over its worklets compute (ref_stage_driver.cpp modes camera, raygen, seed_init, backward, frame).
+FRAMES_FIXTURE = os.path.join(ROOT, "tests", "golden", "ref_frames.npz")
+# name: (driver mode, words per case (None: set by the rows), result word types)
+FRAME_STAGES = {
+    "camera": (12, 12, "f" * 9),      # position, look-at, up, fov, nx, ny -> nlook, delta_x, delta_y
+    "raygen": (13, 14, "fffui"),      # ... work index, seed -> direction, seed after, pixelIndex
+    "seed_init": (14, 1, "u"),        # the stencil value -> WangInit's value of it
+    "backward": (15, None, "ffff"),   # D, S, S x D x (emitted rgba, attenuation rgba) -> the canvas sum rgba
+}
+FRAME_MODE = 16
+N_BACKWARD = 64
+BACKWARD_SHAPES = tuple((d, s) for d in (1, 2, 3, 50) for s in (1, 4))
+CANVASES = ((1, 1), (2, 2), (7, 40), (200, 120), (800, 800), (3840, 2160), (16384, 16384))
+CORNERS_ONLY = (16384, 16384)  # 2^28 rays: taken at its corner indices only
+FRAME_OUTCOMES = OUTCOMES + ("entered_dead",)
+
+
+def cameras() -> dict:
+    """name -> (position, look-at, up, fov): the default view, the scene zoo's, views along every axis with up
+    along another (zeros in nlook, delta_x and delta_y), an up that is not a unit vector, an up nearly parallel to
+    the look vector, a view at 555 scale, and fields of view from 1 to 179 degrees."""
+    import _scenes
+
+    d = (278 / 555.0, 278 / 555.0, -800 / 555.0), (278 / 555.0, 278 / 555.0, 278 / 555.0)
+    h = _scenes.HIGH_CAM
+    c = {
+        "default": (*d, (0, 1, 0), 40.0),
+        "high": (h["position"], h["look_at"], h["view_up"], h["fov_y"]),
+        "skewed_up": ((0.85, 0.7, -1.0), (0.4, 0.45, 0.55), (0.1, 1.0, 0.05), 50.0),
+        "along+x": ((-1.5, 0.5, 0.5), (0.5, 0.5, 0.5), (0, 0, 1), 40.0),
+        "along-x": ((2.5, 0.5, 0.5), (0.5, 0.5, 0.5), (0, 1, 0), 40.0),
+        "along+y": ((0.5, -1.5, 0.5), (0.5, 0.5, 0.5), (1, 0, 0), 40.0),
+        "along-y": ((0.5, 2.5, 0.5), (0.5, 0.5, 0.5), (0, 0, -1), 40.0),
+        "along+z": ((0.5, 0.5, -1.5), (0.5, 0.5, 0.5), (0, 1, 0), 40.0),
+        "along-z": ((0.5, 0.5, 2.5), (0.5, 0.5, 0.5), (1, 0, 0), 40.0),
+        "up_not_unit": (*d, (0, 2, 0), 40.0),
+        "up_nearly_look": ((0.5, 0.5, -1.0), (0.5, 0.5, 0.5), (0, 0.001, 1), 40.0),
+        "scale555": ((278, 278, -800), (278, 278, 278), (0, 1, 0), 40.0),
+        "fov1": (*d, (0, 1, 0), 1.0),
+        "fov90": (*d, (0, 1, 0), 90.0),
+        "fov179": (*d, (0, 1, 0), 179.0),
+        "down_left": ((0.9, 0.9, -0.6), (0.1, 0.2, 0.7), (-0.3, 0.8, 0.2), 65.0),
+        # between the ceiling and the light quad, looking down (a quad's normal is turned to face the ray, so it
+        # still emits), and inside the zoo's emissive sphere, whose outward normal makes it dark from within
+        "above_light": ((0.5, 0.9995, 0.5), (0.5, 0.5, 0.5), (0, 0, 1), 150.0),
+        "in_light_sphere": ((0.85, 0.8, 0.7), (0.5, 0.5, 0.5), (0, 1, 0), 40.0),
+    }
+    return {k: (np.asarray(p, dtype=F), np.asarray(a, dtype=F), np.asarray(u, dtype=F), F(f))
+            for k, (p, a, u, f) in c.items()}
+
+
+AXIS_CAMERAS = ("along+x", "along-x", "along+y", "along-y", "along+z", "along-z")
+
+
+def camera_words(cam, nx, ny) -> np.ndarray:
+    p, a, u, f = cam
+    return np.concatenate([fbits(p), fbits(a), fbits(u), fbits([f]), np.array([nx, ny], dtype=U)])
+
+
+def camera_cases() -> np.ndarray:
+    """Every camera on every canvas: (18 * 7, 12) words."""
+    return np.stack([camera_words(c, nx, ny) for c in cameras().values() for nx, ny in CANVASES])
+
+
+def wang32_np(s):
+    """wangXor.h:30-38, for building and counting cases only."""
+    s = np.asarray(s, dtype=np.uint64) & 0xFFFFFFFF
+    s = (s ^ 61) ^ (s >> 16)
+    s = (s * 9) & 0xFFFFFFFF
+    s = s ^ (s >> 4)
+    s = (s * 0x27D4EB2D) & 0xFFFFFFFF
+    return (s ^ (s >> 15)).astype(U)
+
+
+def _seed_for_draws(first=None, second=None, rnd=None):
+    """A seed whose first (second) hash is the given one; the other draw is whatever follows."""
+    if first is not None:
+        return inv_wang32(first)
+    if second is not None:
+        return inv_wang32(inv_wang32(second))
+    return rnd
+
+
+ONE_HASH = 4294967168  # the lowest hash whose draw is 1.0f (DESIGN.md section 2, RNG known answers)
+HALF_HASH = 1 << 31    # float(2^31) / 4294967295.f = 0.5f
+
+
+def raygen_cases() -> np.ndarray:
+    """(2048, 14) words: camera, canvas, work index, seed.
+      - the four corners and the centre of every canvas (the corners only of the largest), under four cameras;
+      - seeds whose first or second draw is exactly 0 and exactly 1.0f, at corners and random pixels;
+      - the axis cameras on the columns where i + (1 - u) = nx/2 and the rows where j + v = ny/2 with u, v in
+        {0, 0.5, 1}: a component of ray_dir is exactly zero there and the += 0.0000001f runs;
+      - random pixels of random canvases under random cameras."""
+    rs = _rs("raygen")
+    cams = cameras()
+    names = list(cams)
+    rows = []
+
+    def add(cam, nx, ny, idx, seed):
+        rows.append(np.concatenate([camera_words(cams[cam], nx, ny), np.array([idx, seed], dtype=np.uint64).astype(U)]))
+
+    def rseed():
+        return int(rs.randint(0, 1 << 32, dtype=np.uint64))
+
+    k = 0
+    for nx, ny in CANVASES:
+        pix = [0, nx - 1, nx * (ny - 1), nx * ny - 1] + ([] if (nx, ny) == CORNERS_ONLY else [(ny // 2) * nx + nx // 2])
+        for p in pix:
+            for _ in range(4):
+                add(names[k % len(names)], nx, ny, p, rseed())
+                k += 1
+    small = [c for c in CANVASES if c != CORNERS_ONLY]
+    edge_hashes = [0, ONE_HASH, 0xFFFFFFFF, ONE_HASH - 1, 1]
+    for which in ("first", "second"):
+        for t in edge_hashes:
+            for nx, ny in small:
+                for p in (0, nx * ny - 1, int(rs.randint(0, nx * ny))):
+                    add(names[k % len(names)], nx, ny, p, int(_seed_for_draws(**{which: t})))
+                    k += 1
+    # the nudge: (draw hash, pixel coordinate) pairs that make a jitter term exactly zero
+    for cam in AXIS_CAMERAS:
+        for nx, ny in small:
+            cols = [(0, nx // 2 - 1), (ONE_HASH, nx // 2), (0xFFFFFFFF, nx // 2)] if nx % 2 == 0 else [(HALF_HASH, nx // 2)]
+            rows_ = [(0, ny // 2), (ONE_HASH, ny // 2 - 1), (0xFFFFFFFF, ny // 2 - 1)] if ny % 2 == 0 else [(HALF_HASH, ny // 2)]
+            for t, i in cols:
+                if 0 <= i < nx:
+                    for j in sorted({0, ny - 1, int(rs.randint(0, ny))}):
+                        add(cam, nx, ny, j * nx + i, int(inv_wang32(t)))
+            for t, j in rows_:
+                if 0 <= j < ny:
+                    for i in sorted({0, nx - 1, int(rs.randint(0, nx))}):
+                        add(cam, nx, ny, j * nx + i, int(inv_wang32(inv_wang32(t))))
+            # both at once: the second hash is the hash of the first, so the pair is searched among the columns'
+            for t, i in cols:
+                t2 = int(wang32_np(t))
+                v = F(t2) / F(4294967295.0)
+                j = F(ny) / F(2) - v
+                if 0 <= i < nx and j == np.floor(j) and 0 <= j < ny:
+                    add(cam, nx, ny, int(j) * nx + i, int(inv_wang32(t)))
+    while len(rows) < N_STAGE:
+        nx, ny = small[int(rs.randint(0, len(small)))]
+        add(names[int(rs.randint(0, len(names)))], nx, ny, int(rs.randint(0, nx * ny)), rseed())
+    assert len(rows) == N_STAGE, len(rows)
+    return np.stack(rows)
+
+
+def raygen_nudged(cases, camera_out) -> np.ndarray:
+    """(n, 3) bool: the components of ray_dir that are exactly zero before the nudge (Camera.cxx:513-517).  A float32
+    restatement for counting only, like quad_hit_branches; the camera constants are the reference's recorded ones
+    (camera_out rows in camera_cases() order)."""
+    key = {camera_cases()[r, :12].tobytes(): r for r in range(len(camera_out))}
+    con = np.stack([camera_out[key[c[:12].tobytes()]] for c in cases]).view(F)
+    nlook, dx, dy = con[:, 0:3], con[:, 3:6], con[:, 6:9]
+    nx, ny = cases[:, 10].astype(np.int64), cases[:, 11].astype(np.int64)
+    idx = cases[:, 12].astype(np.int64)
+    i, j = (idx % nx).astype(F), (idx // nx).astype(F)
+    t1 = wang32_np(cases[:, 13])
+    t2 = wang32_np(t1)
+    u = t1.astype(F) / F(4294967295.0)
+    v = t2.astype(F) / F(4294967295.0)
+    a = ((F(2) * (i + (F(1) - u)) - nx.astype(F)) / F(2)).astype(F)
+    b = ((F(2) * (j + v) - ny.astype(F)) / F(2)).astype(F)
+    rd = ((nlook + (dx * a[:, None]).astype(F)).astype(F) + (dy * b[:, None]).astype(F)).astype(F)
+    return rd == 0
+
+
+def backward_cases(d: int, s: int) -> np.ndarray:
+    """(64, 2 + 8*s*d) words: per sample and depth emitted rgba and attenuation rgba.  Ordinary paths (emitted mostly
+    0, attenuation 0 .. 2); paths that died on the light at a random depth (emitted 15 there, then attenuation 1 and
+    emitted 0 to the end: CollectIntersecttWorklet's planes of a dead ray); entries with inf, NaN and -0, and
+    0 * inf both ways round."""
+    rs = _rs(f"backward.{d}.{s}")
+    n = N_BACKWARD
+    E = np.where(rs.random_sample((n, s, d, 4)) < 0.8, 0, _uni(rs, 0, 15, (n, s, d, 4))).astype(F)
+    A = _uni(rs, 0, 2, (n, s, d, 4))
+    k = n // 4
+    for r in range(k, 2 * k):  # died on the light
+        for q in range(s):
+            at = int(rs.randint(0, d))
+            E[r, q, :at] = 0
+            E[r, q, at] = F(15)
+            E[r, q, at + 1:] = 0
+            A[r, q, at:] = 1
+    special = np.array([np.inf, -np.inf, np.nan, -0.0, 0.0, FLT_MAX, 1e-45], dtype=F)
+    for r in range(2 * k, 3 * k):  # one special entry somewhere, in either array
+        for q in range(s):
+            arr = E if rs.random_sample() < 0.5 else A
+            arr[r, q, int(rs.randint(0, d)), int(rs.randint(0, 3))] = special[int(rs.randint(0, len(special)))]
+    for r in range(3 * k, n):  # 0 * inf: an infinite radiance under a zero attenuation, and the other way round
+        for q in range(s):
+            at = int(rs.randint(0, d))
+            c = int(rs.randint(0, 3))
+            if rs.random_sample() < 0.5:
+                E[r, q, at, c], A[r, q, :at, c] = np.inf, 0
+            else:
+                E[r, q, at, c] = 0
+                E[r, q, at + 1:, c] = 0
+                A[r, q, :at, c] = np.inf
+    body = np.concatenate([fbits(E), fbits(A)], axis=3).reshape(n, s * d * 8)
+    head = np.tile(np.array([d, s], dtype=U), (n, 1))
+    return np.ascontiguousarray(np.concatenate([head, body], 1))
+
+
+def frame_stage_cases(name: str) -> np.ndarray:
+    if name == "camera":
+        return camera_cases()
+    if name == "raygen":
+        return raygen_cases()
+    if name == "seed_init":
+        return np.array([[1]], dtype=U)  # the constant stencil of MapperPathTracer.cxx:266
+    raise KeyError(name)
+
+
+def driver_frame_stage(name: str, sc, cases, exe: str = REF_STAGES) -> np.ndarray:
+    mode, kin, types = FRAME_STAGES[name]
+    assert kin is None or cases.shape[1] == kin
+    return run_driver(mode, len(types), sc, cases, exe)
+
+
+# name: (scene, camera, nx, ny, spp, depth)
+FRAMES = {
+    "cornell0": ("cornell0", "default", 24, 16, 4, 8),
+    "cornell1": ("cornell1", "default", 24, 16, 4, 8),
+    "cornell2": ("cornell2", "default", 24, 16, 4, 8),
+    "cornell3": ("cornell3", "default", 24, 16, 4, 8),
+    "zoo": ("zoo", "default", 24, 16, 4, 8),
+    "cornell1_deep": ("cornell1", "default", 8, 8, 2, 50),
+    "one_pixel": ("cornell0", "default", 1, 1, 4, 8),
+    "depth1": ("cornell2", "skewed_up", 12, 8, 4, 1),
+    "depth2": ("cornell2", "high", 12, 8, 4, 2),
+    "above_light": ("cornell2", "above_light", 12, 8, 4, 8),
+    "in_light_sphere": ("zoo", "in_light_sphere", 12, 8, 4, 8),
+}
+
+
+def frame_case(name: str) -> np.ndarray:
+    _, cam, nx, ny, spp, depth = FRAMES[name]
+    return np.concatenate([camera_words(cameras()[cam], nx, ny), np.array([spp, depth], dtype=U)]).reshape(1, -1)
+
+
+def driver_frame(name: str, scs, exe: str = REF_STAGES):
+    """The reference's frame: (pixels (n, 5) words: rgb bits, final seed, live count; states (spp, depth, n, 37))."""
+    scn, _, nx, ny, spp, depth = FRAMES[name]
+    n = nx * ny
+    case = frame_case(name)
+    with tempfile.TemporaryDirectory() as td:
+        fin, fout = os.path.join(td, "cases.bin"), os.path.join(td, "results.bin")
+        with open(fin, "wb") as fh:
+            np.array([MAGIC, FRAME_MODE, 1, case.shape[1]], dtype=U).tofile(fh)
+            scene_words(scs[scn]).tofile(fh)
+            case.tofile(fh)
+        subprocess.run([exe, fin, fout], check=True)
+        res = np.fromfile(fout, dtype=U)
+    assert res[:3].tolist() == [FRAME_MODE, 1, 5 * n + spp * depth * n * REC_WORDS], res[:3]
+    return res[3:3 + 5 * n].reshape(n, 5), res[3 + 5 * n:].reshape(spp, depth, n, REC_WORDS)
+
+
+def canonical_states(states) -> np.ndarray:
+    return canonical(np.asarray(states).reshape(-1, REC_WORDS), REC_TYPES).reshape(np.asarray(states).shape)
+
+
+def state_digests(states) -> list:
+    """SHA-256 of all rays' canonical states after every depth of every sample: [sample][depth]."""
+    can = canonical_states(states)
+    return [[digest(can[s, d]) for d in range(can.shape[1])] for s in range(can.shape[0])]
+
+
+def frame_outcomes(sc, states) -> np.ndarray:
+    """(spp, depth, n) int8 index into FRAME_OUTCOMES of what each depth did to each ray, from the recorded states:
+    a ray enters a depth alive at depth 0 (Status = 8, MapperPathTracer.cxx:283) or where the state before has the
+    scatter bit; one that leaves without it has missed (T still FLT_MAX) or ended on the light."""
+    st = canonical_states(states)
+    mt = np.ctypeslib.as_array(sc.mat_type)
+    alive_after = (st[..., REC["status"]] & 8) != 0
+    entered = np.concatenate([np.ones_like(alive_after[:, :1]), alive_after[:, :-1]], 1)
+    T = st[..., REC["T"]].view(F)
+    hit_mt = mt[st[..., REC["M"]].astype(np.int64) % len(mt)]
+    E = st[..., REC["E"]:REC["E"] + 3].view(F)
+    which = st[..., REC["which"]].view(np.int32)
+    out = np.full(alive_after.shape, -1, dtype=np.int8)
+    out[~entered] = 7
+    ended = entered & ~alive_after
+    out[ended & (T == FLT_MAX)] = 0
+    lit = ended & (T != FLT_MAX)
+    assert (hit_mt[lit] == 1).all()
+    out[lit & (E != 0).any(-1)] = 1
+    out[lit & (E == 0).all(-1)] = 2
+    for w in (1, 2, 3):
+        out[entered & alive_after & (hit_mt == 0) & (which == w)] = 2 + w
+    out[entered & alive_after & (hit_mt == 2)] = 6
+    assert (out >= 0).all()
+    return out
+
+
+def frame_coverage(fx) -> dict:
+    """Ray-depths of every outcome over all recorded frames, and the samples that start on a ray whose previous
+    sample had died before its last depth (so that stale normals, points and records are what the dead depths and
+    the next sample find)."""
+    c = {k: 0 for k in FRAME_OUTCOMES}
+    c["sample_after_early_death"] = 0
+    for nm in FRAMES:
+        oc = fx[nm + "_outcome"]
+        for k, v in zip(FRAME_OUTCOMES, np.bincount(oc.reshape(-1), minlength=len(FRAME_OUTCOMES))):
+            c[k] += int(v)
+        c["sample_after_early_death"] += int((oc[:-1, -1] == 7).sum())
+    return c
+
+
+def frame_stage_coverage(fx) -> dict:
+    nud = raygen_nudged(raygen_cases(), fx["camera_out"])
+    c = {f"raygen_nudged_{a}": int(nud[:, k].sum()) for k, a in enumerate("xyz")}
+    cases = raygen_cases()
+    t1 = wang32_np(cases[:, 13])
+    t2 = wang32_np(t1)
+    c["raygen_first_draw_0"], c["raygen_first_draw_1"] = int((t1 == 0).sum()), int((t1 >= ONE_HASH).sum())
+    c["raygen_second_draw_0"], c["raygen_second_draw_1"] = int((t2 == 0).sum()), int((t2 >= ONE_HASH).sum())
+    return c

@@ -13,16 +13,24 @@
 //   constant; Vec<T> op T is per component in T; Vec<T> op Float64 is per
 //   component in double, narrowed to T; Min(x,y) = y < x ? y : x and
 //   Max(x,y) = x < y ? y : x for integers, fmin/fmax for floats; a default
-//   constructed Vec is uninitialised.
+//   constructed Vec is uninitialised; Sum and Multiply are a + b and a * b,
+//   per component on a Vec<Float32, 4>; Algorithm::CopyIf(input, stencil,
+//   output, predicate) writes, in order, the input values whose stencil
+//   value satisfies the predicate.
 #pragma once
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <tuple>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #define VTKM_EXEC
 #define VTKM_CONT
 #define VTKM_EXEC_CONT
+#define VTKM_SUPPRESS_EXEC_WARNINGS
+#define VTKM_IS_DEVICE_ADAPTER_TAG(tag) static_assert(true, "")
 
 namespace vtkm {
 using Id = long long;
@@ -154,11 +162,48 @@ inline Vec<T, 3> TriangleNormal(const Vec<T, 3>& a, const Vec<T, 3>& b, const Ve
   return Cross(b - a, c - a);
 }
 
+// ---- vtkm/BinaryOperators.h
+struct Sum {
+  template <typename T, typename U>
+  auto operator()(const T& a, const U& b) const -> decltype(a + b) { return a + b; }
+};
+struct Multiply {
+  template <typename T, typename U>
+  auto operator()(const T& a, const U& b) const -> decltype(a * b) { return a * b; }
+};
+
+// ---- vtkm/exec: names that PathAlgorithms.h mentions
+namespace exec {
+struct FunctorBase {};
+namespace internal {
+struct ErrorMessageBuffer {};
+} // namespace internal
+} // namespace exec
+
 // ---- vtkm/cont: an ArrayHandle that only lends out plain pointer portals
 namespace cont {
 struct DeviceAdapterTagSerial {};
+struct DeviceAdapterTagAny {};
+struct DeviceAdapterId {};
+struct StorageTagBasic {};
 struct Token {};
 struct ExecutionObjectBase {};
+// Named by PathAlgorithms.h's host-side dispatch templates, which the stage driver never instantiates: it
+// runs the kernel functors of that header itself.
+template <typename Device>
+struct DeviceAdapterAlgorithm;
+namespace internal {
+template <typename In, typename Out>
+struct CopyKernel {
+  CopyKernel(In, Out, Id) {}
+};
+} // namespace internal
+namespace detail {
+template <typename Device, typename T>
+void PrepareArgForExec(T&&, Token&) {}
+} // namespace detail
+template <typename Functor, typename... Args>
+void TryExecuteOnDevice(DeviceAdapterId, Functor&&, Args&&...) {}
 
 template <typename T>
 struct ArrayPortal {
@@ -169,7 +214,7 @@ struct ArrayPortal {
   void Set(Id i, const T& v) const { p[i] = v; }
 };
 
-template <typename T>
+template <typename T, typename Storage = StorageTagBasic>
 class ArrayHandle {
 public:
   template <typename Device>
@@ -191,6 +236,33 @@ public:
 private:
   const T* P = nullptr;
   Id N = 0;
+};
+
+// The implicit arrays and the one algorithm of MapperPathTracer.cxx:265-267.
+template <typename T>
+struct ArrayHandleCounting {
+  T Start, Step;
+  Id N;
+  ArrayHandleCounting(T start, T step, Id n) : Start(start), Step(step), N(n) {}
+  Id GetNumberOfValues() const { return N; }
+  T Get(Id i) const { return static_cast<T>(Start + Step * static_cast<T>(i)); }
+};
+template <typename T>
+struct ArrayHandleConstant {
+  T Value;
+  Id N;
+  ArrayHandleConstant(T value, Id n) : Value(value), N(n) {}
+  Id GetNumberOfValues() const { return N; }
+  T Get(Id) const { return Value; }
+};
+struct Algorithm {
+  // Stream compaction: output = the input values whose stencil value satisfies the predicate, in order.
+  template <typename In, typename Stencil, typename T, typename Predicate>
+  static void CopyIf(const In& input, const Stencil& stencil, std::vector<T>& output, Predicate predicate) {
+    output.clear();
+    for (Id i = 0; i < input.GetNumberOfValues(); ++i)
+      if (predicate(stencil.Get(i))) output.push_back(input.Get(i));
+  }
 };
 } // namespace cont
 

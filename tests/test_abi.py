@@ -81,7 +81,7 @@ def test_signature_table_matches_the_header():
     from raytracingtherestofyourlife_amd import _lib
 
     protos = _prototypes()
-    assert set(protos) == set(_lib.SIGNATURES) and len(protos) == 39
+    assert set(protos) == set(_lib.SIGNATURES) and len(protos) == 40
     assert list(protos) == list(_lib.SIGNATURES), "the table is in the header's order"
     returns = {"rtp_status": ctypes.c_int32, "int32_t": ctypes.c_int32, "const char*": ctypes.c_char_p, "void": None}
     bad = []

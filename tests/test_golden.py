@@ -17,7 +17,8 @@ FULL_FRAMES = ["c2_full"]  # whole frames (byte-plane format, tools/make_golden.
 RENDERS = sorted(n for n in (os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLD, "*.npz")))
                  if n not in FULL_FRAMES and not n.endswith("_digest")  # (digest fixtures: test_gpu_fullsize)
                  and not n.startswith("c5_reduced")  # (reduced-frame fixtures: below)
-                 and n != "ref_stages")  # (the reference's recorded stages, not a render: test_ref_stages.py)
+                 # (the reference's recorded stages and frames, not oracle renders: test_ref_stages.py)
+                 and n not in ("ref_stages", "ref_frames"))
 REDUCED = ["c5_reduced", "c5_reduced_small"]
 
 

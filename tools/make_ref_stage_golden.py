@@ -19,12 +19,25 @@ A 37-word state after each of 13 worklets for 5 x 4096 rays is 39 MB; digests pe
 hashes per ray keep the comparison bit for bit, name the stage and the ray of a mismatch, and fit
 the repository's size limit.
 
+A second file, tests/golden/ref_frames.npz, holds what the reference's code outside the worklet headers computes
+(ref_stage_driver.cpp modes camera, raygen, seed_init, backward, frame):
+  camera_out, raygen_out, seed_init_out, backward_<D>_<S>_out
+                            those stages' results, full
+  <frame>_rgb/_seed/_live   per pixel of a whole small frame: the canvas rgb bits, the final seed, and the depths
+                            the ray entered with the scatter bit set
+  <frame>_outcome           index into _ref_cases.FRAME_OUTCOMES per (sample, depth, ray)
+  meta                      JSON: SHA-256 of every case array, SHA-256 of all rays' states after every depth of
+                            every sample of every frame, the coverage counts
+It is written with fixed zip timestamps, so the same driver gives the same bytes.
+
 Generation fails if an outcome the issue lists has fewer than _ref_cases.MIN_COVER cases."""
 from __future__ import annotations
 
+import io
 import json
 import os
 import sys
+import zipfile
 
 import numpy as np
 
@@ -94,5 +107,57 @@ def main():
     print(rc.FIXTURE, os.path.getsize(rc.FIXTURE), "bytes")
 
 
+def save_npz(path, arrays):
+    """An .npz np.load reads, byte for byte the same for the same arrays (np.savez stamps the time of day)."""
+    with zipfile.ZipFile(path + ".tmp", "w", zipfile.ZIP_DEFLATED) as zf:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(arrays[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue())
+    os.replace(path + ".tmp", path)
+
+
+def frames(path=None):
+    """tests/golden/ref_frames.npz"""
+    scs = rc.scenes(oracle)
+    sc = scs[rc.STAGE_SCENE]  # the stages of this file read no scene; the driver's file format carries one
+    fx, meta = {}, {"cases_sha256": {}, "state_sha256": {}}
+    for name, (_, _, types) in rc.FRAME_STAGES.items():
+        if name == "backward":
+            continue
+        cases = rc.frame_stage_cases(name)
+        meta["cases_sha256"][name] = rc.digest(cases)
+        fx[name + "_out"] = rc.canonical(rc.driver_frame_stage(name, sc, cases), types)
+    for d, s in rc.BACKWARD_SHAPES:
+        cases = rc.backward_cases(d, s)
+        meta["cases_sha256"][f"backward_{d}_{s}"] = rc.digest(cases)
+        fx[f"backward_{d}_{s}_out"] = rc.canonical(rc.driver_frame_stage("backward", sc, cases), "ffff")
+    for nm, (scn, _, nx, ny, spp, depth) in rc.FRAMES.items():
+        meta["cases_sha256"]["frame_" + nm] = rc.digest(np.concatenate([rc.scene_words(scs[scn]), rc.frame_case(nm)[0]]))
+        pix, states = rc.driver_frame(nm, scs)
+        fx[nm + "_rgb"] = rc.canonical(pix[:, :3], "fff")
+        fx[nm + "_seed"], fx[nm + "_live"] = pix[:, 3].copy(), pix[:, 4].copy()
+        meta["state_sha256"][nm] = rc.state_digests(states)
+        fx[nm + "_outcome"] = rc.frame_outcomes(scs[scn], states)
+    meta["coverage"] = {**rc.frame_coverage(fx), **rc.frame_stage_coverage(fx)}
+    print(json.dumps(meta["coverage"], indent=1))
+    low = {k: v for k, v in meta["coverage"].items() if v < rc.MIN_COVER}
+    if low:
+        sys.exit(f"coverage: fewer than {rc.MIN_COVER} cases of {low}")
+    if int(fx["seed_init_out"][0, 0]) == 0:
+        sys.exit("WangInit(1) is 0: CopyIf would copy no seed")
+    fx["meta"] = np.array(json.dumps(meta, sort_keys=True))
+    path = path or rc.FRAMES_FIXTURE
+    save_npz(path, fx)
+    print(path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    main()
+    if not os.path.exists(rc.REF_STAGES):
+        sys.exit(f"{rc.REF_STAGES} is missing: build it where the reference tree is (raytracingtherestofyourlife_amd/build.py)")
+    if "--frames-only" not in sys.argv:
+        main()
+    frames()

@@ -8,6 +8,7 @@
 //            [-o output] [-raw prefix] [-variant 0] [-device 0]
 //            [-rank 0 -world 1] [-dry-run] [-viewbatch N]
 //            [-passes N [-preview]] [-denoise [-levels N]]
+//            [-adaptive T -maxspp M [-passspp P]]
 //
 // Writes <o>.pnm like main.cc, or <o>-<phi>-<theta>.pnm per hemisphere view
 // (generate(), "%.4f" formatting).  -raw additionally dumps the normalised
@@ -33,6 +34,17 @@
 // resumable passes (one pass without -passes) and every other file keeps its
 // bytes.  -denoise with -hemisphere or -direct, or -levels outside 1..8, is an
 // error (exit code 2).
+// -adaptive T -maxspp M [-passspp P]: adaptive sampling of the single view
+// (rtp::ProgressiveRender::Refine, include/rtp_adaptive.h).  -samplecount K is
+// the uniform first pass; then adaptive passes of P samples (default K) over
+// the pixels whose noise estimate exceeds T and whose count stays within M,
+// until a pass selects none.  <o>.pnm (and the -raw dump) is normalised with
+// each pixel's own count (rtp_normalize_counts); <o>-spp.pnm is the
+// sample-count map, grey = (float)count / (float)M on all three channels
+// written by rtp_write_pnm (int(255.99 * grey), no square root).  Without
+// -adaptive every file keeps its bytes.  -adaptive with -hemisphere, -direct,
+// -passes or -denoise, T < 0, M < 1, P < 1 or K < 1, and -maxspp or -passspp
+// without -adaptive, is an error (exit code 2).
 // -direct: the quad mappers' one-bounce AOVs (main.cc:623-651, generate()
 // :399-420): direct.pnm, depth.pnm, normals.pnm, albedo.pnm (or
 // direct-<phi>-<theta>.pnm ... per hemisphere view), all four from one launch.
@@ -91,7 +103,10 @@ int main(int argc, char** argv) {
   int phiCount = 15, thetaCount = 15, rank = 0, world = 1, viewBatch = -1;
   bool hemi = false, dry = false, direct = false, preview = false, havePasses = false;
   int passes = 1, levels = 5;
-  bool denoise = false;
+  bool denoise = false, adaptive = false;
+  float threshold = 0.f;
+  int maxSpp = 0, passSpp = 0;
+  bool haveMaxSpp = false, havePassSpp = false;
   std::string out = "output", raw;
   for (int i = 1; i < argc; i++) {
     auto next = [&](const char* flag) -> const char* {
@@ -114,6 +129,9 @@ int main(int argc, char** argv) {
     else if ((v = next("-viewbatch"))) viewBatch = std::atoi(v);
     else if ((v = next("-passes"))) passes = std::atoi(v), havePasses = true;
     else if ((v = next("-levels"))) levels = std::atoi(v);
+    else if ((v = next("-adaptive"))) threshold = (float)std::atof(v), adaptive = true;
+    else if ((v = next("-maxspp"))) maxSpp = std::atoi(v), haveMaxSpp = true;
+    else if ((v = next("-passspp"))) passSpp = std::atoi(v), havePassSpp = true;
     else if (!std::strcmp(argv[i], "-denoise")) denoise = true;
     else if (!std::strcmp(argv[i], "-preview")) preview = true;
     else if (!std::strcmp(argv[i], "-hemisphere")) hemi = true;
@@ -131,6 +149,17 @@ int main(int argc, char** argv) {
   }
   if (denoise && (hemi || direct || levels < 1 || levels > 8)) {
     std::cerr << "rtp_path: -denoise renders the single view (no -hemisphere, no -direct) with -levels 1..8"
+              << std::endl;
+    return 2;
+  }
+  if (!adaptive && (haveMaxSpp || havePassSpp)) {
+    std::cerr << "rtp_path: -maxspp and -passspp belong to -adaptive T" << std::endl;
+    return 2;
+  }
+  if (adaptive && !havePassSpp) passSpp = s;
+  if (adaptive && (hemi || direct || havePasses || denoise || !(threshold >= 0.f) || maxSpp < 1 || passSpp < 1 || s < 1)) {
+    std::cerr << "rtp_path: -adaptive T -maxspp M [-passspp P] renders the single view (no -hemisphere, -direct, "
+                 "-passes or -denoise) with T >= 0, M >= 1, P >= 1 and -samplecount >= 1"
               << std::endl;
     return 2;
   }
@@ -179,7 +208,21 @@ int main(int argc, char** argv) {
         rtp::SavePNM("albedo" + suffix + ".pnm", b.albedo, x, y);
         return;
       }
-      if (havePasses || denoise) {
+      if (adaptive) {
+        rtp::rendering::MapperPathTracer mapper(s, depth, cb.matIdx, cb.texIdx, cb.matType, cb.texType, cb.tex, dev);
+        mapper.SetLights(cb.lightQuad, cb.lightSphere, cb.ior);
+        rtp::ProgressiveRender r(mapper.UploadScene(cb.ds.GetCellSet(), cb.coord), cam, x, y, depth);
+        r.Step(s);
+        while (r.Refine(passSpp, threshold, maxSpp) > 0) {
+        }
+        r.Canvas(canvas);
+        std::vector<rtp::Vec4f> map(r.Counts().size());
+        for (size_t i = 0; i < map.size(); i++) {
+          const float g = (float)r.Counts()[i] / (float)maxSpp;
+          map[i] = rtp::Vec4f{g, g, g, 0.f};
+        }
+        rtp::SavePNM(out + suffix + "-spp.pnm", map, x, y);
+      } else if (havePasses || denoise) {
         rtp_denoise_params prm = rtp::ProgressiveRender::DefaultDenoiseParams();
         prm.levels = levels;
         rtp::runPathProgressiveRender(x, y, s, depth, canvas, cam, cb, passes, dev,

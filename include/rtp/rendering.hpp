@@ -38,7 +38,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "../rtp.h"
+#include "../rtp_adaptive.h"  // (includes rtp.h)
 
 namespace rtp {
 
@@ -190,6 +190,24 @@ class Device {
                               m2 ? m2->data() : nullptr};
     Check(rtp_render_resume(get(), &camera, nx, ny, spp, depthcount, pixel_ids.empty() ? nullptr : pixel_ids.data(),
                             (int64_t)n, &st, stats));
+  }
+
+  // rtp_refine: one adaptive pass over a host-resident state of the whole
+  // nx x ny canvas and its per-pixel sample counts (include/rtp_adaptive.h):
+  // params.spp more samples of the pixels whose noise exceeds params.threshold
+  // and whose count stays within params.max_spp.  Returns how many it selected.
+  int64_t Refine(const rtp_camera& camera, int nx, int ny, int depthcount, std::vector<Vec4f>& rgba,
+                 std::vector<uint32_t>& seed, std::vector<float>& m2, std::vector<int32_t>& count,
+                 const rtp_refine_params& params, std::vector<uint32_t>* live = nullptr,
+                 rtp_stats* stats = nullptr) const {
+    if (nx <= 0 || ny <= 0) throw ErrorBadValue("Camera width/height must be greater than zero.");
+    const size_t n = (size_t)nx * (size_t)ny;
+    if (rgba.size() != n || seed.size() != n || m2.size() != n || count.size() != n || (live && live->size() != n))
+      throw ErrorBadValue("Refine: the state arrays and the counts must have one entry per pixel");
+    const rtp_render_state st{rgba.data()->data(), seed.data(), live ? live->data() : nullptr, m2.data()};
+    int64_t selected = 0;
+    Check(rtp_refine(get(), &camera, nx, ny, depthcount, &st, count.data(), &params, &selected, stats));
+    return selected;
   }
 
   // rtp_render_guides: what the path camera sees first at each pixel centre
@@ -844,20 +862,39 @@ class ProgressiveRender {
     for (size_t i = 0; i < n; i++) seed_[i] = seed_base + (uint32_t)i;  // seeds[i] = i (uint32 wrap)
     live_.assign(n, 0u);
     m2_.assign(n, 0.f);
+    count_.assign(n, 0);
   }
   // spp more samples of every pixel
   void Step(int spp, rtp_stats* stats = nullptr) {
     device_->RenderResume(cam_, nx_, ny_, spp, depth_, sums_, seed_, &live_, &m2_, {}, stats);
     samples_ += spp;
+    for (int32_t& c : count_) c += spp;
+  }
+  // One adaptive pass (Device::Refine): spp more samples of the pixels whose
+  // noise exceeds threshold and whose count stays within max_spp.  Returns how
+  // many it selected; from the first pass that selects some, the pixels'
+  // counts (Counts()) differ and Samples() keeps the uniform passes' total.
+  int64_t Refine(int spp, float threshold, int max_spp, rtp_stats* stats = nullptr) {
+    const int64_t selected =
+        device_->Refine(cam_, nx_, ny_, depth_, sums_, seed_, m2_, count_, rtp_refine_params{threshold, spp, max_spp},
+                        &live_, stats);
+    if (selected > 0) adaptive_ = true;
+    return selected;
   }
   int64_t Samples() const { return samples_; }
-  // the normalised colours of the samples so far (rtp_normalize) into a canvas of the same size
+  // the samples each pixel has so far (Samples() everywhere until a Refine selects)
+  const std::vector<int32_t>& Counts() const { return count_; }
+  // the normalised colours of the samples so far into a canvas of the same
+  // size: rtp_normalize, or rtp_normalize_counts once the counts differ
   void Canvas(rendering::CanvasRayTracer& canvas) const {
     if (canvas.GetWidth() != nx_ || canvas.GetHeight() != ny_)
       throw ErrorBadValue("ProgressiveRender::Canvas: the canvas must be nx x ny");
     if (samples_ > INT32_MAX) throw ErrorBadValue("ProgressiveRender::Canvas: more than 2^31-1 samples");
     canvas.GetColorBuffer().assign(sums_.begin(), sums_.end());
-    Normalize(canvas.GetColorBuffer(), (int)samples_);
+    if (adaptive_)
+      Check(rtp_normalize_counts(canvas.GetColorBuffer().data()->data(), count_.data(), (int64_t)count_.size()));
+    else
+      Normalize(canvas.GetColorBuffer(), (int)samples_);
   }
   // The denoised preview of the samples so far: resolve, the first-hit guides
   // (rendered once and kept) and the a-trous filter (include/rtp.h), then
@@ -867,6 +904,7 @@ class ProgressiveRender {
   // .denoised gives the same bytes for the same parameters.
   std::vector<Vec4f> Denoised(rtp_denoise_params params = DefaultDenoiseParams()) {
     if (samples_ > INT32_MAX) throw ErrorBadValue("ProgressiveRender::Denoised: more than 2^31-1 samples");
+    if (adaptive_) throw ErrorBadValue("ProgressiveRender::Denoised: not available once Refine has made the counts differ");
     if (!have_guides_) {
       guides_ = device_->RenderGuides(cam_, nx_, ny_);
       have_guides_ = true;
@@ -898,6 +936,8 @@ class ProgressiveRender {
   std::vector<Vec4f> sums_;
   std::vector<uint32_t> seed_, live_;
   std::vector<float> m2_;
+  std::vector<int32_t> count_;
+  bool adaptive_ = false;  // a Refine has selected: the counts differ
   Device::Guides guides_;  // Denoised(): rendered on first use
   bool have_guides_ = false;
 };

@@ -8,6 +8,8 @@ from .mapper import (  # noqa: F401
     Field, default_camera, hemisphere_cameras, normalize, runPath, runPathProgressive, runPathViews, save_pnm,
 )
 from .progressive import ProgressiveRender, noise_from_state, select_active, split_passes  # noqa: F401
+from . import adaptive  # noqa: F401
+from .adaptive import normalize_counts  # noqa: F401
 from .direct import (  # noqa: F401
     Actor, Color, ColorTable, MapperQuad, MapperQuadAlbedo, MapperQuadNormals, Scene, View3D, runAlbedo,
     runDirect, runNorms, runRay, save_depth_pnm,
@@ -19,4 +21,5 @@ __all__ = [
     "Field", "Actor", "Color", "ColorTable", "MapperQuad", "MapperQuadAlbedo", "MapperQuadNormals", "Scene",
     "View3D", "runAlbedo", "runDirect", "runNorms", "runRay", "save_depth_pnm", "hemisphere_cameras", "runPathViews",
     "runPathProgressive", "ProgressiveRender", "noise_from_state", "select_active", "split_passes",
+    "adaptive", "normalize_counts",
 ]

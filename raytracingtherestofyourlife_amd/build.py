@@ -16,8 +16,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librtp.so")
-SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_denoise.hip", "rtp_host.cpp", "rtp_direct_host.cpp", "scene_cornell.cpp"]
-HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h")]
+SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_denoise.hip", "rtp_adaptive.hip", "rtp_host.cpp", "rtp_direct_host.cpp", "rtp_adaptive_host.cpp", "scene_cornell.cpp"]
+HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "rtp_adaptive.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
+           os.path.join("..", "..", "include", "rtp_adaptive.h")]
 ARCH = os.environ.get("RTP_OFFLOAD_ARCH", "gfx950")
 
 
@@ -73,7 +74,8 @@ def build_cpp(force: bool = False) -> list[str]:
     """g++ the C++ host programs against librtp.so (rpath to the package dir)."""
     lib = build()
     built = []
-    hdrs = [os.path.join(ROOT, "include", "rtp.h"), os.path.join(ROOT, "include", "rtp", "rendering.hpp"), lib]
+    hdrs = [os.path.join(ROOT, "include", "rtp.h"), os.path.join(ROOT, "include", "rtp_adaptive.h"),
+            os.path.join(ROOT, "include", "rtp", "rendering.hpp"), lib]
     for exe, src in CPP_PROGRAMS.items():
         rel = os.path.relpath(HERE, os.path.dirname(exe))
         if force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in hdrs + [src]):
@@ -124,6 +126,7 @@ ASAN_DIR = os.path.join(ROOT, "tests", "cpp", "asan")
 ASAN_PROGRAMS = {
     os.path.join(ASAN_DIR, "asan_scene"): os.path.join(ROOT, "tests", "cpp", "asan_scene.cpp"),
     os.path.join(ASAN_DIR, "shim_check"): os.path.join(ROOT, "tests", "cpp", "shim_check.cpp"),
+    os.path.join(ASAN_DIR, "asan_adaptive"): os.path.join(ROOT, "tests", "cpp", "asan_adaptive.cpp"),
 }
 # AddressSanitizer + UBSan on host code only (GPU sanitizers are not available
 # on the pool): each -fsanitize= directly after -Xarch_host.  The sanitizer
@@ -153,7 +156,8 @@ def build_asan(force: bool = False) -> list[str]:
     inc = os.path.join(ROOT, "include")
     built = []
     for exe, src in ASAN_PROGRAMS.items():
-        deps = objs + [src, os.path.join(inc, "rtp.h"), os.path.join(inc, "rtp", "rendering.hpp")]
+        deps = objs + [src, os.path.join(inc, "rtp.h"), os.path.join(inc, "rtp_adaptive.h"),
+                       os.path.join(inc, "rtp", "rendering.hpp")]
         if force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
             # the driver is host C++ (g++-style, like build_cpp), the link
             # pulls in the HIP runtime and the static sanitizer runtimes

@@ -64,6 +64,15 @@ struct rtp_context {
   float quad_lo[3] = {0, 0, 0}, quad_hi[3] = {0, 0, 0};
   float* d_direct = nullptr;
   size_t direct_bytes = 0;
+  // adaptive passes (rtp_adaptive_host.cpp): the selection's scratch (block
+  // counts, total, ids) and the compact state of the selected entries; both
+  // grow on demand, outlive rtp_set_scene like d_hist, and are ordered by
+  // `done` like it.  adapt_ms: the parts of the last timed pass.
+  void* d_adapt_sel = nullptr;
+  size_t adapt_sel_bytes = 0;
+  void* d_adapt_state = nullptr;
+  size_t adapt_state_bytes = 0;
+  double adapt_ms[4] = {0, 0, 0, 0};
 };
 // thread-local last-error message of the C ABI (rtp_host.cpp)
 rtp_status rtp_internal_fail(rtp_status st, const std::string& msg);

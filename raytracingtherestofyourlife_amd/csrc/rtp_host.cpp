@@ -592,7 +592,8 @@ void rtp_destroy(rtp_context* c) {
   (void)drain(c);
   for (void* p : {(void*)c->d_scene, (void*)c->d_hist, (void*)c->d_dbg, (void*)c->d_progress, (void*)c->d_nodes,
                   (void*)c->d_sph_geom, (void*)c->d_sph_all, (void*)c->d_lw_nodes, (void*)c->d_lw_cidx,
-                  (void*)c->d_lw_sph, (void*)c->d_lw_orig, (void*)c->d_cnodes, (void*)c->d_cidx, (void*)c->d_direct})
+                  (void*)c->d_lw_sph, (void*)c->d_lw_orig, (void*)c->d_cnodes, (void*)c->d_cidx, (void*)c->d_direct,
+                  c->d_adapt_sel, c->d_adapt_state})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : {c->ev0, c->ev1, c->done})
     if (e) (void)hipEventDestroy(e);

@@ -1,5 +1,6 @@
 // rtp_host_util.hpp -- what the host translation units of librtp.so share
-// (rtp_host.cpp, rtp_direct_host.cpp, the host half of rtp_denoise.hip):
+// (rtp_host.cpp, rtp_direct_host.cpp, rtp_adaptive_host.cpp, the host half of
+// rtp_denoise.hip):
 // error reporting, environment switches, device buffers of the synchronous
 // entry points, the stats they fill, the timed launch, and the host vector
 // math.  Internal: not installed, nothing here is device code.

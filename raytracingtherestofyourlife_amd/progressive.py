@@ -251,6 +251,44 @@ class ProgressiveRender:
             self.step(spp, active=idx)
         return int(idx.size)
 
+    # ------------------------------------------- adaptive, on the device --
+    def noise_device(self):
+        """The noise estimate as a device tensor float32 [N]
+        (adaptive.noise_device: include/rtp_adaptive.h states it in float32;
+        noise() is the float64 host estimate).  Asynchronous like step()."""
+        import torch
+
+        from . import adaptive
+
+        out = torch.empty(self.n_pixels, dtype=torch.float32, device=self._td)
+        adaptive.noise_device(self.device, self.sums.data_ptr(), self.m2.data_ptr(), self.count.data_ptr(),
+                              self.n_pixels, out.data_ptr(), stream=self._stream())
+        return out
+
+    def refine_device(self, spp: int, threshold: float, max_spp: int) -> int:
+        """refine() without leaving the device (adaptive.refine_device): the
+        estimate, the selection, the gather, the resume pass and the scatter
+        run on the torch current stream; only the number of selected pixels
+        comes back, which is returned.  The rule is refine()'s in float32."""
+        from . import adaptive
+
+        total, _ = adaptive.refine_device(self.device, self.camera, self.nx, self.ny, self.depth,
+                                          self.sums.data_ptr(), self.seed.data_ptr(), self.m2.data_ptr(),
+                                          self.count.data_ptr(), spp, threshold, max_spp,
+                                          live_ptr=self.live.data_ptr(), stream=self._stream())
+        return total
+
+    def converge(self, spp: int, threshold: float, max_spp: int, max_passes: int) -> list:
+        """refine_device passes until one selects nothing or max_passes have
+        run (adaptive.render_adaptive_device): what each pass selected, a
+        final 0 included."""
+        from . import adaptive
+
+        return adaptive.render_adaptive_device(self.device, self.camera, self.nx, self.ny, self.depth,
+                                               self.sums.data_ptr(), self.seed.data_ptr(), self.m2.data_ptr(),
+                                               self.count.data_ptr(), spp, threshold, max_spp, max_passes,
+                                               live_ptr=self.live.data_ptr(), stream=self._stream())
+
     # -------------------------------------------------------- checkpoint --
     def save(self, path: str) -> None:
         """An .npz checkpoint: the state arrays, camera, sizes, depth, seed base."""

@@ -128,6 +128,10 @@ void rtp_destroy(rtp_context* ctx);
  * have reported.  (csrc/rtp_layout.hpp bvh_sphere_pad.) */
 rtp_status rtp_set_scene(rtp_context* ctx, const rtp_scene_desc* scene);
 
+/* More than 256 distinct quads: a mesh scene, the quads in global memory
+ * behind a BVH that the path kernel walks -- include/rtp_mesh.h, which also
+ * lists the entry points below that a mesh scene does not serve yet. */
+
 /* Full canvas render into host memory (rgba_out: float4[nx*ny]). */
 rtp_status rtp_render(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                       int32_t depth, uint32_t seed_base, float* rgba_out, rtp_stats* stats);
@@ -142,7 +146,8 @@ rtp_status rtp_render(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32
  * top edges: their entries outside the canvas are rendered like the others
  * (camera rays past the frame, seeds of no real pixel) and are to be ignored
  * (shard.tile_entries).  Every entry inside the canvas equals
- * rtp_render_device on that pixel, without a pixel list. */
+ * rtp_render_device on that pixel, without a pixel list.
+ * Refused on a mesh scene (rtp_mesh.h): RTP_ERR_INVALID_ARGUMENT, nothing launched. */
 rtp_status rtp_render_tiles_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                                    int32_t depth, uint32_t seed_base, int32_t rank, int32_t world, float* d_rgba_out,
                                    void* hip_stream, rtp_stats* stats);
@@ -169,7 +174,7 @@ rtp_status rtp_render_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx
  * NOT asynchronous like rtp_render_device: the plan is copied to the host and
  * validated before the launch, which waits for the work already queued on
  * hip_stream (an experiment's entry point: a bad plan is an error, not a
- * silently clamped launch). */
+ * silently clamped launch).  Refused on a mesh scene (rtp_mesh.h). */
 rtp_status rtp_render_planned_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
                                      int32_t depth, uint32_t seed_base, int64_t pixel_begin, int64_t pixel_count,
                                      const int64_t* d_pixel_ids, const int32_t* d_wave_begin, int32_t n_waves,
@@ -287,7 +292,8 @@ rtp_status rtp_render_resume(rtp_context* ctx, const rtp_camera* cam, int32_t nx
  *        (kind 0 quad, 1 sphere).  Miss: -1.
  * Asynchronous on hip_stream; stats != NULL synchronises (kernel_ms).
  * RTP_ERR_INVALID_ARGUMENT / RTP_ERR_NO_SCENE, nothing launched: a NULL
- * camera, a bad size or field of view, every output NULL, no scene set. */
+ * camera, a bad size or field of view, every output NULL, no scene set, a
+ * mesh scene (rtp_mesh.h; and with the guides the denoised preview). */
 rtp_status rtp_render_guides_device(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny, float* d_g0,
                                     float* d_g1, int32_t* d_prim, void* hip_stream, rtp_stats* stats);
 /* Host buffers, synchronous. */
@@ -395,7 +401,8 @@ typedef struct {
 
 /* Host buffers (nullable each, at least one non-NULL): rgba float4[nx*ny] per
  * AOV, depth float[nx*ny].  aovs is informational: an AOV is rendered iff its
- * buffer is non-NULL.  Synchronous. */
+ * buffer is non-NULL.  Synchronous.  Refused, like rtp_render_direct_device,
+ * on a mesh scene (rtp_mesh.h). */
 rtp_status rtp_render_direct(rtp_context* ctx, const rtp_camera* cam, int32_t nx, int32_t ny,
                              const rtp_direct_desc* desc, float* color_rgba, float* normals_rgba,
                              float* albedo_rgba, float* depth, rtp_stats* stats);
@@ -487,7 +494,10 @@ int32_t rtp_debug_counters(rtp_context* ctx, uint64_t* out, int32_t n_out);
 /* Diagnostics: the closest hit of n rays (o, d: 6 floats each, host memory)
  * through the quad prefilter and through the exact scan of every quad.
  * out (host, 7 u32 per ray): prefiltered (t bits, kind, index), exact (t
- * bits, kind, index), 1 if the ray fell back to the exact scan. */
+ * bits, kind, index), 1 if the ray fell back to the exact scan.  On a mesh
+ * scene (rtp_mesh.h): the walk's (t bits, kind, the caller's quad index or the
+ * sphere index), the same from the device's brute-force scan of every mesh
+ * quad, then 3. */
 rtp_status rtp_debug_closest_hit(rtp_context* ctx, const float* rays, int64_t n, uint32_t* out);
 
 /* Diagnostics: one depth of the path kernel's bounce (intersect, collect,

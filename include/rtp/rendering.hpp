@@ -32,6 +32,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -39,6 +40,7 @@
 #include <vector>
 
 #include "../rtp_adaptive.h"  // (includes rtp.h)
+#include "../rtp_mesh.h"
 
 namespace rtp {
 
@@ -596,7 +598,27 @@ class MapperPathTracer {
     for (int k = 0; k < 4; k++) d.light_quad_points[k] = light_quad_[k];
     d.light_sphere_point = light_sphere_;
     d.ior = ior_;
-    Check(rtp_set_scene(device(), &d));
+    // more than 256 distinct quads (rtp_set_scene's inline limit): a mesh scene, the quads behind a BVH (rtp_mesh.h)
+    Check(DistinctQuads(d) > 256 ? rtp_set_scene_mesh(device(), &d) : rtp_set_scene(device(), &d));
+  }
+  // Quads that differ from every earlier one in a vertex (bit for bit, in order), the material or the texture:
+  // what rtp_set_scene keeps.  (Bad ids count as distinct: the library reports them.)
+  static size_t DistinctQuads(const rtp_scene_desc& d) {
+    if (d.n_quads <= 256) return (size_t)std::max(d.n_quads, 0);
+    if (!d.points || !d.quad_points || !d.quad_mat || !d.quad_tex) return (size_t)d.n_quads;  // (the library refuses it)
+    typedef std::array<uint32_t, 14> Key;
+    std::vector<Key> keys((size_t)d.n_quads);
+    for (int32_t q = 0; q < d.n_quads; q++) {
+      Key& k = keys[(size_t)q];
+      for (int c = 0; c < 4; c++) {
+        const int32_t id = d.quad_points[4 * q + c];
+        if (id < 0 || id >= d.n_points) return (size_t)d.n_quads;
+        std::memcpy(&k[3 * (size_t)c], d.points + 3 * (size_t)id, 12);
+      }
+      k[12] = (uint32_t)d.quad_mat[q], k[13] = (uint32_t)d.quad_tex[q];
+    }
+    std::sort(keys.begin(), keys.end());
+    return (size_t)(std::unique(keys.begin(), keys.end()) - keys.begin());
   }
 
   std::shared_ptr<Internals> internals_;

@@ -1,0 +1,52 @@
+/* rtp_mesh.h -- mesh scenes: quad meshes of any size behind a BVH in the path
+ * kernel.  Additions to the C ABI of rtp.h (RTP_ABI_VERSION stays 3); the
+ * functions are exported from librtp.so like those of rtp.h. */
+#ifndef RTP_MESH_H
+#define RTP_MESH_H
+#include "rtp.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* A mesh scene: the same descriptor with any number of quads from 1 to 2^22
+ * (rtp_set_scene holds at most 256 distinct quads inline).  The quads are kept
+ * in global memory behind a BVH that the path kernel walks -- always, also
+ * for 18 quads -- and at most 8 spheres are scanned inline; with 9 or more
+ * spheres the call returns RTP_ERR_INVALID_ARGUMENT (no quad BVH together
+ * with a sphere BVH).  Ids, materials, the light quad and the light sphere are
+ * checked as by rtp_set_scene, with its messages.  A refused call leaves the
+ * previous scene in place; rtp_set_scene replaces a mesh scene and the other
+ * way round.  Duplicate quads are kept: a later copy never wins.
+ *
+ * The closest hit is unchanged: the minimum of (t, quads before spheres, index
+ * in the caller's list) over the hits with t > 0.001, every quad tested with
+ * the general float32 arithmetic.  The boxes only cull, and the promise has a
+ * limit like the sphere BVH's: the walk equals the brute-force scan for every
+ * ray (a) whose origin lies within `reach` -- 2 diagonals of the scene's
+ * bounding box -- of the vertices of the quad the scan reports, and (b) that
+ * meets that quad's first-triangle plane (v00, v10, v01) with |cos(theta)| >=
+ * cos_min = 2^-8, theta the angle to the plane's normal.  Outside it (origins
+ * far away, rays within 0.22 degrees of the plane) the float32 test accepts
+ * points arbitrarily far from the quad, and the walk may miss what the scan
+ * would report.  A quad whose fourth vertex is off the first triangle's plane
+ * by 1/512 or more of its distance beyond the diagonal gets an unbounded box:
+ * always tested, sound, slow -- a mesh made mostly of such quads renders as
+ * slowly as a brute-force scan.  rtp_mesh_guarantee returns cos_min and reach of
+ * the current mesh scene.  (csrc/rtp_layout.hpp kMeshCosMin.)
+ *
+ * On a mesh scene rtp_render, rtp_render_device (range and pixel list; work
+ * stealing), rtp_render_pixels, rtp_render_resume*, rtp_render_views* (the
+ * per-view loop), rtp_debug_closest_hit and rtp_debug_bounce work.  Refused
+ * with RTP_ERR_INVALID_ARGUMENT, nothing launched: rtp_render_tiles_device,
+ * rtp_render_planned_device, rtp_render_guides* (and the denoised preview),
+ * rtp_render_direct*, and every render under RTP_KERNEL=1 or
+ * RTP_DEBUG_STATS=1.  RTP_MESH_SCAN=1 (read by this call) makes every render
+ * of the scene scan all its quads instead of walking: the A/B handle. */
+rtp_status rtp_set_scene_mesh(rtp_context* ctx, const rtp_scene_desc* scene);
+rtp_status rtp_mesh_guarantee(rtp_context* ctx, float* cos_min, float* reach);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RTP_MESH_H */

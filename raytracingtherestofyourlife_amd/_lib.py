@@ -150,6 +150,11 @@ def _signatures() -> dict:
 
 SIGNATURES = _signatures()
 EXPORTED_SYMBOLS = list(SIGNATURES)
+# include/rtp_mesh.h (mesh scenes), bound by load() with the table above
+MESH_SIGNATURES = {
+    "rtp_set_scene_mesh": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc)]),
+    "rtp_mesh_guarantee": (ctypes.c_int32, [vp, f32p, f32p]),
+}
 
 
 class RtpError(RuntimeError):
@@ -189,7 +194,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     # baselines of the tools/*_bench.py): it loads without them, and calling
     # one raises AttributeError.  The in-tree library must export them all.
     missing = []
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **MESH_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:

@@ -16,9 +16,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librtp.so")
-SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_denoise.hip", "rtp_adaptive.hip", "rtp_host.cpp", "rtp_direct_host.cpp", "rtp_adaptive_host.cpp", "scene_cornell.cpp"]
-HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "rtp_adaptive.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
-           os.path.join("..", "..", "include", "rtp_adaptive.h")]
+SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_denoise.hip", "rtp_adaptive.hip", "rtp_host.cpp", "rtp_direct_host.cpp", "rtp_adaptive_host.cpp", "rtp_mesh_host.cpp",
+           "scene_cornell.cpp"]
+HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "rtp_adaptive.hpp", "rtp_bvh_host.hpp", "rtp_mesh.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
+           os.path.join("..", "..", "include", "rtp_adaptive.h"), os.path.join("..", "..", "include", "rtp_mesh.h")]
 ARCH = os.environ.get("RTP_OFFLOAD_ARCH", "gfx950")
 
 
@@ -67,6 +68,7 @@ ROOT = os.path.dirname(HERE)
 CPP_PROGRAMS = {
     os.path.join(ROOT, "examples", "rtp_path"): os.path.join(ROOT, "examples", "path_main.cpp"),
     os.path.join(ROOT, "tests", "cpp", "shim_check"): os.path.join(ROOT, "tests", "cpp", "shim_check.cpp"),
+    os.path.join(ROOT, "tests", "cpp", "mesh_mapper"): os.path.join(ROOT, "tests", "cpp", "mesh_mapper.cpp"),
 }
 
 
@@ -75,7 +77,7 @@ def build_cpp(force: bool = False) -> list[str]:
     lib = build()
     built = []
     hdrs = [os.path.join(ROOT, "include", "rtp.h"), os.path.join(ROOT, "include", "rtp_adaptive.h"),
-            os.path.join(ROOT, "include", "rtp", "rendering.hpp"), lib]
+            os.path.join(ROOT, "include", "rtp_mesh.h"), os.path.join(ROOT, "include", "rtp", "rendering.hpp"), lib]
     for exe, src in CPP_PROGRAMS.items():
         rel = os.path.relpath(HERE, os.path.dirname(exe))
         if force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in hdrs + [src]):
@@ -127,6 +129,7 @@ ASAN_PROGRAMS = {
     os.path.join(ASAN_DIR, "asan_scene"): os.path.join(ROOT, "tests", "cpp", "asan_scene.cpp"),
     os.path.join(ASAN_DIR, "shim_check"): os.path.join(ROOT, "tests", "cpp", "shim_check.cpp"),
     os.path.join(ASAN_DIR, "asan_adaptive"): os.path.join(ROOT, "tests", "cpp", "asan_adaptive.cpp"),
+    os.path.join(ASAN_DIR, "asan_mesh"): os.path.join(ROOT, "tests", "cpp", "asan_mesh.cpp"),
 }
 # AddressSanitizer + UBSan on host code only (GPU sanitizers are not available
 # on the pool): each -fsanitize= directly after -Xarch_host.  The sanitizer

@@ -33,6 +33,13 @@ struct rtp_context {
   int32_t* d_lw_orig = nullptr;
   int lw_bytes = 0;  // its LDS footprint (0: the scene has no LDS walk)
   bool use_bvh = false;
+  // a mesh scene (rtp_set_scene_mesh): the quads behind their BVH in global
+  // memory (DevScene::mesh_*), and the reach of its promise
+  bool is_mesh = false;
+  uint32_t* d_mesh_nodes = nullptr;
+  rtp::DevQuad* d_mesh_quads = nullptr;
+  float* d_mesh_shade = nullptr;
+  float mesh_reach = 0.f;
   int oct_mask = 0;  // the global walk's octant mask (DevScene::oct_mask) of the current scene
   int ff_policy = 0;  // rtp_ff_policy (RNG jump tables)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

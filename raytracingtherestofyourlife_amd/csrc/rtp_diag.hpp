@@ -84,6 +84,53 @@ __global__ void __launch_bounds__(256) rtp_eval_bounce_kernel(const DevScene* __
   w[14] = ps.nonfinite ? 1u : 0u;
 }
 
+// The same two on a mesh scene (rtp_set_scene_mesh).  Closest hit: the walk
+// of the mesh BVH (t bits, kind, the caller's quad index or the sphere index),
+// then the brute-force scan of every mesh quad with the same per-lane test,
+// then 3.
+__global__ void __launch_bounds__(256) rtp_eval_closest_mesh_kernel(const DevScene* __restrict__ sc,
+                                                                    const float* __restrict__ rays, uint32_t* out,
+                                                                    int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * i;
+  const f3 o = mk(r[0], r[1], r[2]), d = mk(r[3], r[4], r[5]);
+  const Hit a = closest_hit_mesh<false>(sc, o, d);
+  const Hit b = closest_hit_mesh<true>(sc, o, d);
+  uint32_t* w = out + 7 * i;
+  w[0] = __float_as_uint(a.t), w[1] = (uint32_t)a.kind, w[2] = (uint32_t)a.idx;
+  w[3] = __float_as_uint(b.t), w[4] = (uint32_t)b.kind, w[5] = (uint32_t)b.idx;
+  w[6] = 3u;
+}
+// One depth on a mesh scene: the closest hit by the walk (the scan under
+// RTP_MESH_SCAN=1, as the renders), then shade_hit's mesh variant.
+__global__ void __launch_bounds__(256) rtp_eval_bounce_mesh_kernel(const DevScene* __restrict__ sc,
+                                                                   const float* __restrict__ rays,
+                                                                   const uint32_t* __restrict__ seeds, uint32_t* out,
+                                                                   int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * i;
+  Path ps;
+  ps.org = mk(r[0], r[1], r[2]);
+  ps.dir = mk(r[3], r[4], r[5]);
+  ps.d = 0;
+  ps.nonfinite = false;
+  uint32_t seed = seeds[i];
+  f3 emit = mk(0.f, 0.f, 0.f);
+  float4 a0 = make_float4(1.f, 1.f, 1.f, 0.f);
+  const Hit h = sc->mesh_scan ? closest_hit_mesh<true>(sc, ps.org, ps.dir) : closest_hit_mesh<false>(sc, ps.org, ps.dir);
+  const int res = shade_hit<false, false, true>(sc, ps, seed, emit, &a0, 2, nullptr, h);
+  uint32_t* w = out + 15 * i;
+  w[0] = (uint32_t)res;
+  w[1] = __float_as_uint(emit.x), w[2] = __float_as_uint(emit.y), w[3] = __float_as_uint(emit.z);
+  w[4] = __float_as_uint(a0.x), w[5] = __float_as_uint(a0.y), w[6] = __float_as_uint(a0.z);
+  w[7] = __float_as_uint(ps.org.x), w[8] = __float_as_uint(ps.org.y), w[9] = __float_as_uint(ps.org.z);
+  w[10] = __float_as_uint(ps.dir.x), w[11] = __float_as_uint(ps.dir.y), w[12] = __float_as_uint(ps.dir.z);
+  w[13] = seed;
+  w[14] = ps.nonfinite ? 1u : 0u;
+}
+
 // First-hit guides of a path camera (rtp_render_guides_device), one lane per
 // pixel: the ray through the pixel centre (camera_ray_at with 0.5f for both
 // jitter draws), the path kernel's closest_hit, and of that hit the normal

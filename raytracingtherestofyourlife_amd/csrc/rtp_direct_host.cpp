@@ -194,6 +194,8 @@ rtp_status check_direct(rtp_context* c, const rtp_camera* cam, int32_t nx, int32
                         bool any_out) {
   if (!c || !cam || !dd) return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: NULL argument");
   RTP_TRY(check_canvas_camera(c, cam, nx, ny, "render_direct"));
+  if (c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: not available on a mesh scene (rtp_set_scene_mesh)");
   if (!any_out) return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: no output buffer");
   if (c->n_ref_quads > 0 && !dd->quad_scalar)
     return fail(RTP_ERR_INVALID_ARGUMENT, "render_direct: quad_scalar is NULL");

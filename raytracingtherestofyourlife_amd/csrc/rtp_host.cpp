@@ -20,9 +20,12 @@
 #include <vector>
 
 #include "../../include/rtp.h"
+#include "../../include/rtp_mesh.h"
 #include "rtp_context.hpp"
+#include "rtp_bvh_host.hpp"
 #include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
+#include "rtp_mesh.hpp"
 
 extern "C" const char* rtp_instance_name(int variant, int stats, int walk, int tiles, int plan, int steal, int views,
                                          int resume);
@@ -390,98 +393,7 @@ FfSnap ff_tables(int device, int policy, uint64_t samples) {
 // test accepts, and the point it returns, lie inside it, and the kernel
 // compares against a slack-widened [0, t_best] interval.  The
 // closest hit is the lexicographic min of (t, kind, index) whatever the order.
-struct BvhPrim {
-  float lo[3], hi[3], cen[3];
-  int32_t idx;
-};
-struct TNode {
-  float lo[3], hi[3];
-  int axis = 0, left = -1, right = -1, first = 0, count = 0;
-};
-
-float half_area(const float lo[3], const float hi[3]) {
-  const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-  return dx * dy + dy * dz + dz * dx;
-}
-
-int bvh_build(std::vector<BvhPrim>& P, int b, int e, std::vector<TNode>& T, std::vector<int32_t>& order,
-              int leaf_size = rtp::kBvhLeafSize) {
-  const int me = (int)T.size();
-  T.emplace_back();
-  TNode nd;
-  float clo[3], chi[3];
-  for (int k = 0; k < 3; k++) {
-    nd.lo[k] = clo[k] = INFINITY;
-    nd.hi[k] = chi[k] = -INFINITY;
-  }
-  for (int i = b; i < e; i++)
-    for (int k = 0; k < 3; k++) {
-      nd.lo[k] = std::min(nd.lo[k], P[i].lo[k]);
-      nd.hi[k] = std::max(nd.hi[k], P[i].hi[k]);
-      clo[k] = std::min(clo[k], P[i].cen[k]);
-      chi[k] = std::max(chi[k], P[i].cen[k]);
-    }
-  const int n = e - b;
-  if (n <= leaf_size) {
-    nd.first = (int)order.size();
-    nd.count = n;
-    for (int i = b; i < e; i++) order.push_back(P[i].idx);
-    T[me] = nd;
-    return me;
-  }
-  // binned SAH
-  constexpr int kBins = 16;
-  int best_ax = -1, best_split = 0;
-  float best_cost = INFINITY;
-  for (int ax = 0; ax < 3; ax++) {
-    const float ext = chi[ax] - clo[ax];
-    if (!(ext > 0)) continue;
-    int cnt[kBins] = {};
-    float blo[kBins][3], bhi[kBins][3];
-    for (int j = 0; j < kBins; j++)
-      for (int k = 0; k < 3; k++) blo[j][k] = INFINITY, bhi[j][k] = -INFINITY;
-    for (int i = b; i < e; i++) {
-      int j = (int)((P[i].cen[ax] - clo[ax]) / ext * kBins);
-      j = std::min(kBins - 1, std::max(0, j));
-      cnt[j]++;
-      for (int k = 0; k < 3; k++) blo[j][k] = std::min(blo[j][k], P[i].lo[k]), bhi[j][k] = std::max(bhi[j][k], P[i].hi[k]);
-    }
-    for (int s = 1; s < kBins; s++) {  // split between bins s-1 and s
-      float llo[3] = {INFINITY, INFINITY, INFINITY}, lhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      float rlo[3] = {INFINITY, INFINITY, INFINITY}, rhi[3] = {-INFINITY, -INFINITY, -INFINITY};
-      int nl = 0, nr = 0;
-      for (int j = 0; j < kBins; j++) {
-        if (!cnt[j]) continue;
-        float* lo = j < s ? llo : rlo;
-        float* hi = j < s ? lhi : rhi;
-        (j < s ? nl : nr) += cnt[j];
-        for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], blo[j][k]), hi[k] = std::max(hi[k], bhi[j][k]);
-      }
-      if (!nl || !nr) continue;
-      const float cost = nl * half_area(llo, lhi) + nr * half_area(rlo, rhi);
-      if (cost < best_cost) best_cost = cost, best_ax = ax, best_split = s;
-    }
-  }
-  int mid;
-  if (best_ax >= 0) {
-    const int ax = best_ax;
-    const float ext = chi[ax] - clo[ax];
-    auto bin = [&](const BvhPrim& x) {
-      return std::min(kBins - 1, std::max(0, (int)((x.cen[ax] - clo[ax]) / ext * kBins)));
-    };
-    mid = (int)(std::stable_partition(P.begin() + b, P.begin() + e, [&](const BvhPrim& x) { return bin(x) < best_split; }) -
-                P.begin());
-    nd.axis = ax;
-  } else {  // coincident centroids: median split by index
-    std::sort(P.begin() + b, P.begin() + e, [](const BvhPrim& x, const BvhPrim& y) { return x.idx < y.idx; });
-    mid = b + n / 2;
-    nd.axis = 0;
-  }
-  nd.left = bvh_build(P, b, mid, T, order, leaf_size);
-  nd.right = bvh_build(P, mid, e, T, order, leaf_size);
-  T[me] = nd;
-  return me;
-}
+// (BvhPrim, TNode, bvh_build and the threaded flattening: rtp_bvh_host.hpp, shared with the mesh BVH)
 
 // inner nodes of the sphere BVH above this depth are dropped from the walks'
 // arrays (bvh_flatten below)
@@ -504,44 +416,27 @@ constexpr float kBvhDropArea = 0.6f;  // (0: off)
 // that reaches it would hit its box with about that probability: dropping it
 // saves one visit when it would be hit and costs one when it would not).
 void bvh_flatten(const std::vector<TNode>& T, int t, int oct, const std::vector<int32_t>& order,
-                 const std::vector<rtp::DevSphere>& sph, std::vector<rtp::BvhNode>& out, int depth = 0,
-                 int drop = 0, float drop_sa = 0.f, float parent_area = 0.f) {
-  const TNode& n = T[t];
-  const float area = half_area(n.lo, n.hi);
-  const bool inner2 = n.left >= 0 && T[n.left].left >= 0 && T[n.right].left >= 0;
-  if (n.left >= 0 && (depth < drop || (drop_sa > 0.f && inner2 && parent_area > 0.f && area > drop_sa * parent_area))) {
-    const bool neg = (oct >> n.axis) & 1;
-    const float pa = parent_area > 0.f ? parent_area : area;  // the nearest emitted ancestor's (or the root's)
-    bvh_flatten(T, neg ? n.right : n.left, oct, order, sph, out, depth + 1, drop, drop_sa, pa);
-    bvh_flatten(T, neg ? n.left : n.right, oct, order, sph, out, depth + 1, drop, drop_sa, pa);
-    return;
-  }
-  const int me = (int)out.size();
-  out.emplace_back();
-  rtp::BvhNode nd{};
-  const TNode& s = T[t];
-  std::memcpy(nd.lo, s.lo, sizeof(nd.lo));
-  std::memcpy(nd.hi, s.hi, sizeof(nd.hi));
-  if (s.left < 0) {
-    if (RTP_BVH_EMBED && s.count == 1) {
-      const rtp::DevSphere& S = sph[order[s.first]];
-      std::memcpy(nd.lo, S.c, sizeof(nd.lo));
-      nd.hi[0] = S.rr;
-      int32_t orig = order[s.first];
-      std::memcpy(&nd.hi[1], &orig, sizeof(orig));
-      nd.hi[2] = 0.f;
-      nd.leaf = rtp::kBvhLeafSphere;
-    } else {
-      nd.leaf = (s.first << 3) | s.count;
-    }
-  } else {
-    const bool neg = (oct >> s.axis) & 1;  // moving toward lower coordinates: right (upper) child first
-    bvh_flatten(T, neg ? s.right : s.left, oct, order, sph, out, depth + 1, drop, drop_sa, area);
-    bvh_flatten(T, neg ? s.left : s.right, oct, order, sph, out, depth + 1, drop, drop_sa, area);
-    nd.leaf = 0;
-  }
-  nd.skip = (int32_t)out.size();
-  out[me] = nd;
+                 const std::vector<rtp::DevSphere>& sph, std::vector<rtp::BvhNode>& out, int drop = 0,
+                 float drop_sa = 0.f) {
+  bvh_thread(
+      T, t, oct, out,
+      [&](const TNode& s, rtp::BvhNode& nd) {
+        if (RTP_BVH_EMBED && s.count == 1) {
+          const rtp::DevSphere& S = sph[order[s.first]];
+          std::memcpy(nd.lo, S.c, sizeof(nd.lo));
+          nd.hi[0] = S.rr;
+          int32_t orig = order[s.first];
+          std::memcpy(&nd.hi[1], &orig, sizeof(orig));
+          nd.hi[2] = 0.f;
+          nd.leaf = rtp::kBvhLeafSphere;
+        } else {
+          nd.leaf = (s.first << 3) | s.count;
+        }
+      },
+      [&](const TNode& n, int depth, float area, float parent_area) {
+        const bool inner2 = T[n.left].left >= 0 && T[n.right].left >= 0;
+        return !(depth < drop || (drop_sa > 0.f && inner2 && parent_area > 0.f && area > drop_sa * parent_area));
+      });
 }
 
 }  // namespace
@@ -593,7 +488,8 @@ void rtp_destroy(rtp_context* c) {
   for (void* p : {(void*)c->d_scene, (void*)c->d_hist, (void*)c->d_dbg, (void*)c->d_progress, (void*)c->d_nodes,
                   (void*)c->d_sph_geom, (void*)c->d_sph_all, (void*)c->d_lw_nodes, (void*)c->d_lw_cidx,
                   (void*)c->d_lw_sph, (void*)c->d_lw_orig, (void*)c->d_cnodes, (void*)c->d_cidx, (void*)c->d_direct,
-                  c->d_adapt_sel, c->d_adapt_state})
+                  (void*)c->d_mesh_nodes, (void*)c->d_mesh_quads, (void*)c->d_mesh_shade, c->d_adapt_sel,
+                  c->d_adapt_state})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : {c->ev0, c->ev1, c->done})
     if (e) (void)hipEventDestroy(e);
@@ -627,15 +523,15 @@ struct SceneBuild {
   std::vector<rtp::BvhNode> lw_nodes;
   std::vector<int32_t> lw_order;
   int lw_per_oct = 0;
+  // a mesh scene: its BVH (rtp_mesh_host.cpp) and the records it is uploaded as
+  bool mesh = false;
+  MeshBuild mb;
+  std::vector<uint32_t> mesh_cnodes;       // 8 * n_nodes compact nodes
+  std::vector<rtp::DevQuad> mesh_quads;    // leaf order
+  std::vector<float> mesh_shade;           // 8 floats per quad, the caller's order
 };
 
-bool pt_ok(const rtp_scene_desc* s, int32_t id) { return id >= 0 && id < s->n_points; }
-bool mat_ok(const rtp_scene_desc* s, int32_t m) {
-  return m >= 0 && m < s->n_mat && s->mat_type[m] >= 0 && s->mat_type[m] <= 2;
-}
-bool tex_ok(const rtp_scene_desc* s, int32_t t) {
-  return t >= 0 && t < s->n_tex_type && s->tex_type[t] >= 0 && s->tex_type[t] < s->n_tex;
-}
+// (pt_ok, mat_ok, tex_ok: rtp_host_util.hpp, shared with the mesh builder)
 
 // The quads: validated, de-duplicated, grouped by kind, with the prefilter
 // tables and the -direct mode's bounds.  Quads that repeat an earlier quad
@@ -832,7 +728,7 @@ void scene_sphere_bvh(const rtp_scene_desc* s, SceneBuild& B) {
     int per_oct = 0;
     for (int oct = 0; oct < 8; oct++) {  // 8 copies of n_nodes entries, indices local to each copy
       std::vector<rtp::BvhNode> one;
-      bvh_flatten(tree, 0, oct & oct_mask, order, sph, one, 0, drop, drop_sa);
+      bvh_flatten(tree, 0, oct & oct_mask, order, sph, one, drop, drop_sa);
       per_oct = (int)one.size();  // (the same nodes are dropped in every octant's order)
       nodes.insert(nodes.end(), one.begin(), one.end());
     }
@@ -850,7 +746,7 @@ void scene_sphere_bvh(const rtp_scene_desc* s, SceneBuild& B) {
       bvh_build(P2, 0, s->n_spheres, tree2, lw_order, rtp::kLdsWalkLeaf);
       for (int oct = 0; oct < 8; oct++) {
         std::vector<rtp::BvhNode> one;
-        bvh_flatten(tree2, 0, oct, lw_order, sph, one, 0, drop, drop_sa);
+        bvh_flatten(tree2, 0, oct, lw_order, sph, one, drop, drop_sa);
         lw_per_oct = (int)one.size();
         lw_nodes.insert(lw_nodes.end(), one.begin(), one.end());
       }
@@ -992,9 +888,11 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
   c->use_bvh = false;
   c->lw_bytes = 0;
   c->oct_mask = 0;
+  c->is_mesh = false;
   for (void** p : {(void**)&c->d_nodes, (void**)&c->d_sph_geom, (void**)&c->d_sph_all, (void**)&c->d_cnodes,
                    (void**)&c->d_cidx, (void**)&c->d_lw_nodes, (void**)&c->d_lw_cidx, (void**)&c->d_lw_sph,
-                   (void**)&c->d_lw_orig})
+                   (void**)&c->d_lw_orig, (void**)&c->d_mesh_nodes, (void**)&c->d_mesh_quads,
+                   (void**)&c->d_mesh_shade})
     if (*p) {
       const hipError_t e = hipFree(*p);
       *p = nullptr;
@@ -1013,7 +911,22 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
     h->cnodes = c->d_cnodes;
     h->cidx = c->d_cidx;
   }
+  if (B.mesh) {
+    const size_t nb = B.mesh_cnodes.size() * 4, qb = B.mesh_quads.size() * sizeof(rtp::DevQuad),
+                 sb = B.mesh_shade.size() * 4;
+    UPLOAD_TRY(hipMalloc(&c->d_mesh_nodes, nb));
+    UPLOAD_TRY(hipMalloc(&c->d_mesh_quads, qb));
+    UPLOAD_TRY(hipMalloc(&c->d_mesh_shade, sb));
+    UPLOAD_TRY(hipMemcpy(c->d_mesh_nodes, B.mesh_cnodes.data(), nb, hipMemcpyHostToDevice));
+    UPLOAD_TRY(hipMemcpy(c->d_mesh_quads, B.mesh_quads.data(), qb, hipMemcpyHostToDevice));
+    UPLOAD_TRY(hipMemcpy(c->d_mesh_shade, B.mesh_shade.data(), sb, hipMemcpyHostToDevice));
+    h->mesh_nodes = c->d_mesh_nodes;
+    h->mesh_quads = c->d_mesh_quads;
+    h->mesh_shade = c->d_mesh_shade;
+  }
   UPLOAD_TRY(hipMemcpy(c->d_scene, h, sizeof(*h), hipMemcpyHostToDevice));
+  c->is_mesh = B.mesh;
+  c->mesh_reach = B.mesh ? B.mb.reach : 0.f;
   c->lw_bytes = h->n_lw_nodes > 0 ? 16 * (8 * h->n_lw_nodes + h->n_lw_sph) : 0;
   c->use_bvh = B.use_bvh;
   c->oct_mask = B.use_bvh ? h->oct_mask : 0;
@@ -1039,9 +952,66 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
   return scene_upload(c, s, B);
 }
 
+// A mesh scene (include/rtp_mesh.h): every quad behind the mesh BVH in global
+// memory -- none inline, so the device scene's n_quads is 0 and the inline
+// scans and LDS tables are empty -- and at most 8 spheres inline.  Every
+// refusal comes before the upload: the previous scene stays.
+rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
+  if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh: NULL argument");
+  SceneBuild B;
+  B.mesh = true;
+  RTP_TRY(mesh_build(s, B.mb));
+  rtp::DevScene* h = B.h.get();
+  std::memset(h, 0, sizeof(*h));
+  h->oct_mask = 7;
+  RTP_TRY(scene_spheres(s, B));  // (fewer than kBvhMinSpheres: no sphere BVH)
+  scene_sphere_bvh(s, B);
+  RTP_TRY(scene_lights(s, B));
+  const int n = s->n_quads;
+  B.mesh_quads.resize(n);
+  B.mesh_shade.assign((size_t)8 * n, 0.f);
+  for (int j = 0; j < n; j++) {
+    const int q = B.mb.order[j];
+    const int32_t* id = s->quad_points + 4 * q;
+    rtp::DevQuad& Q = B.mesh_quads[j];
+    fill_quad(Q, ld(s->points + 3 * id[0]), ld(s->points + 3 * id[1]), ld(s->points + 3 * id[2]),
+              ld(s->points + 3 * id[3]));
+    Q.mt = s->mat_type[s->quad_mat[q]];
+    st(Q.alb, ld(s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]]));
+    Q.orig = q;
+    Q.key_lo = (uint32_t)q;  // the caller's index: the hit's index and the tie-break of equal t
+    float* sh = B.mesh_shade.data() + (size_t)8 * q;
+    std::memcpy(sh, Q.n, 12);
+    std::memcpy(sh + 3, Q.alb, 12);
+    std::memcpy(sh + 6, &Q.mt, 4);
+  }
+  B.mesh_cnodes.resize((size_t)4 * B.mb.nodes.size());
+  mesh_compact(B.mb.nodes.data(), (int64_t)B.mb.nodes.size(), B.mesh_cnodes.data());
+  h->n_mesh_nodes = B.mb.n_nodes;
+  h->n_mesh_quads = n;
+  h->mesh_scan = env_is("RTP_MESH_SCAN", '1') ? 1 : 0;
+  for (int k = 0; k < 3; k++) B.blo[k] = 0.f, B.bhi[k] = 0.f;  // (-direct mode is refused on a mesh scene)
+  return scene_upload(c, s, B);
+}
+
+rtp_status rtp_mesh_guarantee(rtp_context* c, float* cos_min, float* reach) {
+  if (!c || !c->has_scene || !c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_mesh_guarantee: the context holds no mesh scene");
+  if (cos_min) *cos_min = rtp::kMeshCosMin;
+  if (reach) *reach = c->mesh_reach;
+  return RTP_OK;
+}
+
 }  // extern "C"
 
 namespace {
+
+// the entry points a mesh scene does not serve yet (include/rtp_mesh.h): refused before anything is launched
+rtp_status refuse_mesh(const rtp_context* c, const char* who) {
+  if (c && c->has_scene && c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available on a mesh scene (rtp_set_scene_mesh)");
+  return RTP_OK;
+}
 
 // pathtracing::Camera::SetParameters -> CreateRaysImpl -> RayGen ctor
 void camera_setup(const rtp_camera* cam, int32_t nx, int32_t ny, rtp::DevCamera* out) {
@@ -1126,7 +1096,10 @@ rtp_status plan_launch(rtp_context* c, const RenderJob& j, LaunchPlan& pl) {
   // takes the global walk, same results: the instance table answers)
   const bool lds_walk = c->lw_bytes > 0 && rtp_instance_name(2, pl.stats_on, 2, j.tile != nullptr, j.d_wave_begin != nullptr,
                                                              0, j.d_views != nullptr, j.resume) != nullptr;
-  pl.bvh = !c->use_bvh ? 0 : lds_walk ? 2 : 1;
+  pl.bvh = c->is_mesh ? 3 : !c->use_bvh ? 0 : lds_walk ? 2 : 1;
+  if (c->is_mesh && (pl.stats_on || env_is("RTP_KERNEL", '1')))
+    return fail(RTP_ERR_INVALID_ARGUMENT,
+                "render: RTP_KERNEL=1 and RTP_DEBUG_STATS=1 are not available on a mesh scene (rtp_set_scene_mesh)");
   pl.lanes = rtp_plan_history_lanes(j.npix, j.spp, pl.bvh, pl.stats_on, &pl.variant, &pl.waves);
   if (j.d_wave_begin) {  // a planned launch: the caller's waves
     if (pl.variant != 2 || c->use_bvh || j.tile)
@@ -1305,6 +1278,7 @@ rtp_status rtp_render_planned_device(rtp_context* c, const rtp_camera* cam, int3
                                      const int64_t* d_pixel_ids, const int32_t* d_wave_begin, int32_t n_waves,
                                      float* d_rgba_out, const rtp_pixel_aux* aux, void* hip_stream, rtp_stats* stats) {
   RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
+  RTP_TRY(refuse_mesh(c, "rtp_render_planned_device"));
   if (pixel_count <= 0 || !d_rgba_out || !d_wave_begin || n_waves <= 0 || n_waves > (1 << 24))
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_planned_device: bad plan / output");
   if (!d_pixel_ids && (pixel_begin < 0 || pixel_begin + pixel_count > (int64_t)nx * ny))
@@ -1338,6 +1312,7 @@ rtp_status rtp_render_tiles_device(rtp_context* c, const rtp_camera* cam, int32_
                                    int32_t depth, uint32_t seed_base, int32_t rank, int32_t world, float* d_rgba_out,
                                    void* hip_stream, rtp_stats* stats) {
   RTP_TRY(check_render_args(c, cam, nx, ny, spp, depth));
+  RTP_TRY(refuse_mesh(c, "rtp_render_tiles_device"));
   if (world < 1 || rank < 0 || rank >= world)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_render_tiles_device: rank outside [0, world)");
   const int64_t tx = (nx + 15) / 16, ty = (ny + 15) / 16;
@@ -1453,7 +1428,7 @@ rtp_status acquire_view_table(rtp_context* c, int32_t n, size_t* slot) {
 // the batched launch unless the scene or the environment asks for the
 // per-view loop (include/rtp.h rtp_render_views_device)
 bool views_batched(const rtp_context* c) {
-  return !c->use_bvh && !env_is("RTP_KERNEL", '1') && !env_is("RTP_DEBUG_STATS", '1') &&
+  return !c->use_bvh && !c->is_mesh && !env_is("RTP_KERNEL", '1') && !env_is("RTP_DEBUG_STATS", '1') &&
          !env_is("RTP_VIEWS_BATCH", '0');
 }
 
@@ -1567,6 +1542,7 @@ rtp_status launch_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, int3
 }
 rtp_status check_guides_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, bool any_output) {
   RTP_TRY(check_render_args(c, cam, nx, ny, 0, 1));
+  RTP_TRY(refuse_mesh(c, "render_guides"));
   if (!any_output) return fail(RTP_ERR_INVALID_ARGUMENT, "render_guides: every output is NULL");
   return RTP_OK;
 }
@@ -1661,7 +1637,7 @@ rtp_status rtp_debug_closest_hit(rtp_context* c, const float* rays, int64_t n, u
   uint32_t* dout = nullptr;
   HIP_TRY_AS("rtp_debug_closest_hit", b.get(&din, (size_t)n * 24, rays));
   HIP_TRY_AS("rtp_debug_closest_hit", b.get(&dout, (size_t)n * 28));
-  HIP_TRY_AS("rtp_debug_closest_hit", rtp_launch_eval_closest(c->d_scene, din, dout, n, c->use_bvh ? 1 : 0, nullptr));
+  HIP_TRY_AS("rtp_debug_closest_hit", rtp_launch_eval_closest(c->d_scene, din, dout, n, c->is_mesh ? 3 : c->use_bvh ? 1 : 0, nullptr));
   HIP_TRY_AS("rtp_debug_closest_hit", DevBufs::back(out, dout, (size_t)n * 28));
   return RTP_OK;
 }
@@ -1680,7 +1656,7 @@ rtp_status rtp_debug_bounce(rtp_context* c, const float* rays, const uint32_t* s
   HIP_TRY_AS("rtp_debug_bounce", b.get(&din, (size_t)n * 24, rays));
   HIP_TRY_AS("rtp_debug_bounce", b.get(&dseed, (size_t)n * 4, seeds));
   HIP_TRY_AS("rtp_debug_bounce", b.get(&dout, (size_t)n * 60));
-  HIP_TRY_AS("rtp_debug_bounce", rtp_launch_eval_bounce(c->d_scene, din, dseed, dout, n, c->use_bvh ? 1 : 0, nullptr));
+  HIP_TRY_AS("rtp_debug_bounce", rtp_launch_eval_bounce(c->d_scene, din, dseed, dout, n, c->is_mesh ? 3 : c->use_bvh ? 1 : 0, nullptr));
   HIP_TRY_AS("rtp_debug_bounce", DevBufs::back(out, dout, (size_t)n * 60));
   return RTP_OK;
 }

@@ -153,4 +153,13 @@ inline rtp_status check_canvas_camera(const rtp_context* c, const rtp_camera* ca
   return RTP_OK;
 }
 
+// the index checks of a scene descriptor (rtp_set_scene and rtp_set_scene_mesh)
+inline bool pt_ok(const rtp_scene_desc* s, int32_t id) { return id >= 0 && id < s->n_points; }
+inline bool mat_ok(const rtp_scene_desc* s, int32_t m) {
+  return m >= 0 && m < s->n_mat && s->mat_type[m] >= 0 && s->mat_type[m] <= 2;
+}
+inline bool tex_ok(const rtp_scene_desc* s, int32_t t) {
+  return t >= 0 && t < s->n_tex_type && s->tex_type[t] >= 0 && s->tex_type[t] < s->n_tex;
+}
+
 }  // namespace rtp_host

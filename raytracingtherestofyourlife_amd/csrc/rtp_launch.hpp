@@ -14,7 +14,7 @@ namespace {
 enum : unsigned { kStats = 1, kTiles = 2, kPlan = 4, kSteal = 8, kViews = 16, kResume = 32, kLockstep = 64 };
 struct Instance {
   unsigned modes;
-  int walk;  // the sphere BVH: 0 none, 1 the global threaded walk, 2 the LDS walk
+  int walk;  // the sphere BVH: 0 none, 1 the global threaded walk, 2 the LDS walk; 3: a mesh scene's quad BVH
   const void* fn;
   int threads;   // per block
   bool dyn_lds;  // takes the LDS walk's tree as dynamic LDS
@@ -25,7 +25,7 @@ struct Instance {
 #define POOL(modes, walk, ...) RTP_ROW(modes, walk, 64 * rtp::kWavesPerBlock, false, __VA_ARGS__)
 #define LDS(modes, ...) RTP_ROW(modes, 2, 64 * rtp::kLdsBvhWavesPerBlock, true, __VA_ARGS__)
 // Every render-kernel instance there is; a mode without a row is refused.
-// rtp_render_pool<kStats, kBvh, kTiles, kPlan, kSteal, kViews, kResume>, rtp_render_pool_lds<kTiles, kSteal>.
+// rtp_render_pool<kStats, kBvh, kTiles, kPlan, kSteal, kViews, kResume, kMesh>, rtp_render_pool_lds<kTiles, kSteal>.
 const Instance kInstances[] = {
     // lockstep: a pixel list or range only
     RTP_ROW(kLockstep, 0, 256, false, rtp_render_lockstep<false>),
@@ -59,6 +59,11 @@ const Instance kInstances[] = {
     LDS(kTiles, rtp_render_pool_lds<true, false>),
     LDS(kSteal, rtp_render_pool_lds<false, true>),
     LDS(kSteal | kTiles, rtp_render_pool_lds<true, true>),
+    // a mesh scene (walk 3): {plain, stealing} x {render, resume}
+    POOL(0, 3, rtp_render_pool<false, false, false, false, false, false, false, true>),
+    POOL(kSteal, 3, rtp_render_pool<false, false, false, false, true, false, false, true>),
+    POOL(kResume, 3, rtp_render_pool<false, false, false, false, false, false, true, true>),
+    POOL(kResume | kSteal, 3, rtp_render_pool<false, false, false, false, true, false, true, true>),
 };
 #undef LDS
 #undef POOL
@@ -104,7 +109,7 @@ int device_cus(int* dev_out = nullptr) {  // 0: no device
 }
 // the waves of the plain instance <stats, walk> that fit the chip at once
 int pool_resident_waves(bool stats, int walk) {
-  static int cached[2][3] = {{-1, -1, -1}, {-1, -1, -1}};
+  static int cached[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
   int& c = cached[stats][walk];
   if (c > 0) return c;
   int dev = 0;
@@ -134,13 +139,15 @@ int pool_resident_waves(bool stats, int walk) {
 // larger than this would leave blocks waiting for a free CU, and their
 // statically assigned first entries would run as a tail after the stolen work.
 int steal_resident_waves(int walk) {
-  static int cached[2] = {-1, -1};
-  int& c = cached[walk ? 1 : 0];
+  static int cached[3] = {-1, -1, -1};
+  const int wk = walk == 3 ? 3 : walk ? 1 : 0;  // (a mesh scene has no tile-deal instance)
+  int& c = cached[wk == 3 ? 2 : wk];
   if (c > 0) return c;
   const int cus = device_cus();
   if (cus == 0) return 1024;
-  const int nb = std::min(blocks_per_cu(find_instance(kSteal, walk ? 1 : 0), 0),
-                          blocks_per_cu(find_instance(kSteal | kTiles, walk ? 1 : 0), 0));
+  const int nb = wk == 3 ? blocks_per_cu(find_instance(kSteal, 3), 0)
+                         : std::min(blocks_per_cu(find_instance(kSteal, wk), 0),
+                                    blocks_per_cu(find_instance(kSteal | kTiles, wk), 0));
   c = cus * nb * rtp::kWavesPerBlock;
   return c;
 }
@@ -255,7 +262,8 @@ extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const 
                                               int64_t n, int bvh, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
-  if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_closest_kernel<true>, g, b, 0, stream, scene, rays, out, n);
+  if (bvh == 3) hipLaunchKernelGGL(rtp::rtp_eval_closest_mesh_kernel, g, b, 0, stream, scene, rays, out, n);
+  else if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_closest_kernel<true>, g, b, 0, stream, scene, rays, out, n);
   else hipLaunchKernelGGL(rtp::rtp_eval_closest_kernel<false>, g, b, 0, stream, scene, rays, out, n);
   return hipGetLastError();
 }
@@ -263,7 +271,8 @@ extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const f
                                              uint32_t* out, int64_t n, int bvh, hipStream_t stream) {
   if (n <= 0) return hipSuccess;
   const dim3 g((unsigned)((n + 255) / 256)), b(256);
-  if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<true>, g, b, 0, stream, scene, rays, seeds, out, n);
+  if (bvh == 3) hipLaunchKernelGGL(rtp::rtp_eval_bounce_mesh_kernel, g, b, 0, stream, scene, rays, seeds, out, n);
+  else if (bvh) hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<true>, g, b, 0, stream, scene, rays, seeds, out, n);
   else hipLaunchKernelGGL(rtp::rtp_eval_bounce_kernel<false>, g, b, 0, stream, scene, rays, seeds, out, n);
   return hipGetLastError();
 }

@@ -23,6 +23,14 @@ constexpr int kBvhGpuMinSpheres = 262144;  // from this size the BVH is built on
 #define RTP_BVH_LEAF 1  // measured best on C3: 1 < 2 < 4 < 7 (367 / 407 / 469 / 564 ms at 16 spp)
 #endif
 constexpr int kBvhLeafSize = RTP_BVH_LEAF;  // leaf size bound (<= 7: 3-bit count field)
+constexpr int kMaxQuadsMesh = 1 << 22;    // quads of a mesh scene (rtp_set_scene_mesh): global memory, behind a BVH
+#ifndef RTP_MESH_LEAF
+// measured on terrains of 2^14 / 2^18 quads (kernel ms, 512^2 x 16 spp): leaf 1: 8.7 / 30.3, 2: 8.9 / 26.9,
+// 4: 10.1 / 27.1, 7: 10.5 / 27.9 (profiles/mesh_bench.txt); 1 also takes four times the nodes of 4
+#define RTP_MESH_LEAF 2
+#endif
+constexpr int kMeshLeaf = RTP_MESH_LEAF;  // quads per leaf of the mesh BVH (<= 7: 3-bit count field)
+static_assert(kMeshLeaf >= 1 && kMeshLeaf <= 7, "a leaf's count has 3 bits");
 
 // Zero-structure kinds of quads: the masks of the nonzero components of the
 // edge vectors (e01, e03, e21, e23).  A kind's test (quad_hit_masked) drops
@@ -148,6 +156,64 @@ inline float bvh_sphere_pad(float cx, float cy, float cz, float r, float reach) 
   return slab + (__builtin_sqrtf(r * r + E) - r) + kBvhReachRound * reach;
 }
 
+// The pad of a mesh quad's box (rtp_mesh_host.cpp; the walk: rtp_trace.hpp
+// mesh_visit).  As for the spheres the boxes only cull, which is sound only
+// if every ray that the float32 quad test (quad_hit_masked<0>) accepts for a
+// quad crosses every box around it with the point at the accepted t inside.
+// Three things widen what the test accepts beyond the exact quad.
+//
+// 1. No upper bound on alpha, beta.  The test rejects alpha < 0, beta < 0,
+//    t < 0 and, when alpha + beta > 1, the second triangle's ap < 0, bp < 0;
+//    t is always the first triangle's plane P1 (v00, v10, v01).  With
+//    alpha + beta <= 1 the point p = o + t d is in the first triangle.
+//    Otherwise the ray meets the second triangle's plane P2 at p2 in the cone
+//    (ap, bp >= 0) at v11.  If ap + bp <= 1, p2 is in the second triangle and
+//    at most h from P1 (h: the distance of v11 from P1), so |p - p2| =
+//    dist(p2, P1) / sin(phi) <= h / |cos(theta)| (phi the ray's angle to P1,
+//    theta its angle to P1's normal).  If ap + bp > 1 too, p lies a > 0 beyond
+//    the diagonal L (v10, v01) on P1 and p2 lies b > 0 beyond it on P2, on the
+//    other side; P1 and P2 meet in L at the fold angle psi, tan(psi) = h / w
+//    (w: how far v11's projection on P1 lies beyond L).  Then dist(p2, P1) =
+//    b sin(psi) and |p2 - p| >= a + b cos(psi), so sin(phi) <= tan(psi): for a
+//    planar quad never, for a bent one only for rays flatter than the fold --
+//    and then p is unbounded (the reference reports such hits).  A quad with
+//    tan(psi) >= kMeshCosMin / 2 (or w <= 0, or a corner angle whose sine is
+//    below kMeshMinSine) is therefore "strongly non-planar" and gets an
+//    unbounded box: it is tested by every ray, slow and sound.  For the
+//    others the term is h / kMeshCosMin.
+// 2. Roundings, u = 2^-24, D = |o - v| <= reach, A = |e01 x e03| =
+//    |e01| |e03| s (s: the sine of the corner angle), to first order:
+//      P = d x e03           |dP|    <=  6 u |d| |e03|   (2 products, 1 sum per component)
+//      det = e01 . P         |ddet|  <=  9 u |d| |e01| |e03|;  det = |d| A cos(theta)
+//      T = o - v00           |dT|    <=  2 u D
+//      T . P                 |.|     <= (2 + 6 + 3) u D |d| |e03|  = 11 u D |d| |e03|
+//      Q = T x e01           |dQ|    <=  8 u D |e01|
+//      d . Q, e03 . Q        |.|     <= 11 u D |d| |e01|,  11 u D |e01| |e03|
+//      1 / det, the products 2 u relative, and det's 9 u / (s cos(theta))
+//    Through their numerators alpha, beta and t each move the point by
+//    11 u D / (s cos(theta)) (alpha along e01, beta along e03, t along d):
+//    33 u reach / (s cos(theta)).  Through 1 / det and the last product each
+//    moves it by its own length times (9 / (s cos(theta)) + 2) u <= 11 u /
+//    (s cos(theta)): alpha |e01| and beta |e03| are at most an edge each near
+//    the quad (<= one diagonal = reach / 2), t |d| = |p - o| <= D + a
+//    diagonal <= 1.5 reach: 2.5 * 11 u reach / (s cos(theta)).  In all the
+//    accepted region grows by less than 60.5 u reach / (s cos(theta)); the
+//    pad takes 64 (kMeshRound).  Unbounded for rays in the plane: hence cos_min.
+// 3. The slab test's own roundings, as for the spheres: v_rcp_f32's ulp and
+//    one rounding of o / d, 2^-22 (|o| + |box|) in space; covered by
+//    1e-5 + 2^-16 max|coordinate| + 2^-18 reach.
+// The promise (include/rtp_mesh.h rtp_set_scene_mesh): the walk equals the scan
+// for every ray whose origin is within `reach` (kBvhReachFactor diagonals of
+// the scene's bounding box) of the winning quad's vertices and that meets the
+// quad's first-triangle plane with |cos(theta)| >= kMeshCosMin.  kMeshCosMin
+// = 2^-8: on the Cornell box (diagonal 1.73, s = 1) the pad is 2^-18 * 3.46 *
+// 256 = 3.4e-3, 0.2% of the diagonal on each side of every box -- the cull
+// it costs; rays within 0.22 degrees of a quad's plane are outside the promise.
+constexpr float kMeshCosMin = 0x1p-8f;
+constexpr float kMeshRound = 0x1p-18f;    // 64 * 2^-24
+constexpr float kMeshMinSine = 0x1p-10f;  // flatter corners: the unbounded box
+constexpr float kMeshHuge = 0x1p100f;     // the unbounded box's half extent (rounds to +-inf in half precision)
+
 // leaf value of a one-sphere leaf that holds the sphere itself: lo = centre,
 // hi[0] = radius^2, hi[1] = sphere index (int bits)
 constexpr int32_t kBvhLeafSphere = -1;
@@ -268,6 +334,17 @@ struct alignas(16) DevScene {
   // (fewer distinct copies: a smaller footprint in the texture cache)
   int32_t oct_mask;
   int32_t pad3[2];
+  // Mesh scenes (rtp_set_scene_mesh; n_quads == 0: no inline quad, empty LDS
+  // tables): the quads in global memory in the leaf order of a threaded BVH of
+  // 8 octant copies of compact nodes (the sphere BVH's 16-byte format; leaves
+  // kCBvhLeafBit | first << 3 | count).  DevQuad::key_lo is the quad's index
+  // in the caller's list (32 bits: the hit's index, the tie-break of equal t).
+  const uint32_t* mesh_nodes;  // 8 * n_mesh_nodes compact nodes
+  const DevQuad* mesh_quads;   // n_mesh_quads records, leaf order
+  const float* mesh_shade;     // 8 floats per quad in the caller's order: n, alb, mt, 0 (the qshade record)
+  int32_t n_mesh_nodes, n_mesh_quads;
+  int32_t mesh_scan;           // RTP_MESH_SCAN=1: renders scan every mesh quad instead of walking
+  int32_t pad4[3];
 };
 // The pool kernel's scans prefetch up to two records past the last quad or
 // prefilter record; these must stay inside DevScene (values never used).

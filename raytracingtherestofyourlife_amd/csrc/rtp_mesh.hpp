@@ -1,0 +1,45 @@
+// rtp_mesh.hpp -- the device-free builder of a mesh scene's quad BVH
+// (rtp_mesh_host.cpp), used by rtp_set_scene_mesh (rtp_host.cpp).  Internal.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "../../include/rtp_mesh.h"
+#include "rtp_layout.hpp"
+
+namespace rtp_host {
+
+struct MeshBuild {
+  int n_nodes = 0;                  // nodes per octant copy
+  std::vector<rtp::BvhNode> nodes;  // 8 * n_nodes: one threaded copy per ray-direction octant
+  std::vector<int32_t> order;       // leaf order: the caller's quad index of each stored quad
+  std::vector<float> boxes;         // 6 per quad, the caller's order: the padded box (lo, hi)
+  std::vector<float> pads;          // per quad: the pad (kMeshHuge: the unbounded box)
+  float reach = 0.f;                // the promise's reach (kBvhReachFactor scene diagonals)
+};
+
+// the descriptor checks of rtp_set_scene_mesh (rtp_set_scene's, and the mesh scene's counts)
+rtp_status mesh_validate(const rtp_scene_desc* s);
+// validate, pad, build (binned SAH, leaves of <= leaf_size quads) and thread the 8 octant copies
+rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& out, int leaf_size = rtp::kMeshLeaf);
+// BvhNodes -> the walk's 16-byte compact nodes (half-precision boxes rounded outward)
+void mesh_compact(const rtp::BvhNode* nodes, int64_t total, uint32_t* out);
+
+}  // namespace rtp_host
+
+// The builder for tests and stand-alone programs (exported from librtp.so, not
+// part of rtp.h; no device is touched).  nodes (32 bytes each, at most
+// node_cap; 2 * n_quads always suffice) receives octant `oct`'s copy, order
+// the leaf order, boxes 6 floats per quad, pads one; guarantee: cos_min, reach.
+// Every output is optional.
+extern "C" rtp_status rtp_mesh_build_host(const rtp_scene_desc* scene, int32_t oct, int32_t node_cap, int32_t* n_nodes,
+                                          void* nodes, int32_t* order, float* boxes, float* pads, float* guarantee);
+// Internal test hooks, exported beside it and likewise no part of any public
+// header: the leaf size the library was built with; mesh_compact over n
+// BvhNodes; and a brute-force scan of a descriptor's quads on the host in
+// float32 (the reference's quad test restated; tests/test_mesh_host.py holds
+// every t it accepts to the oracle's quad_hit stage bit for bit).
+extern "C" int32_t rtp_mesh_leaf_size(void);
+extern "C" void rtp_mesh_compact_host(const void* nodes, int64_t n, uint32_t* out);
+extern "C" rtp_status rtp_mesh_scan_host(const rtp_scene_desc* scene, const float* rays, int64_t n, uint32_t* out);
+

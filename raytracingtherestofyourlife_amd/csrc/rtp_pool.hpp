@@ -237,10 +237,13 @@ typedef const __attribute__((address_space(1))) uint32_t GU32;
 // per slot (PoolSlots::m2), added where the sample is added to the sums.
 // One instance's modes, by name (the seven of rtp_render_pool's template
 // signature, in its order); LdsBvh: rtp_render_pool_lds's 16-wave block.
-template <bool Stats, bool Bvh, bool Tiles, bool Plan, bool Steal, bool Views, bool Resume, bool LdsBvh = false>
+// Mesh: a mesh scene (rtp_set_scene_mesh): the quads behind the mesh BVH,
+// walked resumably like the sphere BVH (rtp_trace.hpp mesh_visit).
+template <bool Stats, bool Bvh, bool Tiles, bool Plan, bool Steal, bool Views, bool Resume, bool LdsBvh = false,
+          bool Mesh = false>
 struct PoolCfg {
   static constexpr bool kStats = Stats, kBvh = Bvh, kTiles = Tiles, kPlan = Plan, kSteal = Steal, kViews = Views,
-                        kResume = Resume, kLdsBvh = LdsBvh;
+                        kResume = Resume, kLdsBvh = LdsBvh, kMesh = Mesh;
   static constexpr int kWPB = LdsBvh ? kLdsBvhWavesPerBlock : kWavesPerBlock;  // waves per block
 };
 
@@ -353,7 +356,8 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
                                           unsigned char* smem, float* s_qshade, uint32_t* s_bvh,
                                           uint32_t* s_entry_all, float* s_m2_all) {
   constexpr bool kStats = Cfg::kStats, kBvh = Cfg::kBvh, kTiles = Cfg::kTiles, kPlan = Cfg::kPlan,
-                 kLdsBvh = Cfg::kLdsBvh, kSteal = Cfg::kSteal, kViews = Cfg::kViews, kResume = Cfg::kResume;
+                 kLdsBvh = Cfg::kLdsBvh, kSteal = Cfg::kSteal, kViews = Cfg::kViews, kResume = Cfg::kResume,
+                 kMesh = Cfg::kMesh;
   constexpr int kWPB = Cfg::kWPB;
   const int lane = threadIdx.x & 63;
   const int wib = threadIdx.x >> 6;
@@ -653,7 +657,45 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     const unsigned long long ta = stamp(want_dbg);
     unsigned long long tbnc = ta;
     bool shade = has_path;
-    if constexpr (kBvh) {
+    if constexpr (kMesh) {
+      // The resumable search of a mesh scene, with the sphere walk's rule
+      // (RTP_WALK_DONE): a new ray scans the inline spheres, then walks the
+      // mesh BVH from node 0 -- or, under RTP_MESH_SCAN=1 (wave-uniform),
+      // tests every quad in storage order, wni counting quads instead of nodes.
+      const bool scan = sc->mesh_scan != 0;
+      const int nn = scan ? sc->n_mesh_quads : sc->n_mesh_nodes;
+      if (has_path && wni < 0) {
+        wh = mesh_spheres(sc, ps.org, ps.dir);
+        wni = 0;
+      }
+      const uint64_t pm = __ballot(has_path);
+      const int need = min(RTP_WALK_DONE, __popcll(pm));
+      bool walking = has_path && wni < nn;
+      if (__ballot(walking)) {
+        const f3 o = ps.org, d = ps.dir;
+        const MeshRay R = mesh_ray(sc, o, d);
+        GF4* __restrict__ quads = (GF4*)sc->mesh_quads;
+        u4v v = u4v{0u, 0u, 0u, 0u};
+        if (walking && !scan) v = R.nodes[wni];
+        for (;;) {
+          const uint64_t wm = __ballot(walking);
+          if (wm == 0 || __popcll(pm & ~wm) >= need) break;
+          if (walking) {
+            int next;
+            if (scan) {
+              mesh_quad_test(quads, wni, o, d, wh);
+              next = wni + 1;
+            } else {
+              next = mesh_visit(quads, R, o, d, v, wni, wh);
+            }
+            walking = next < nn;
+            if (walking && !scan) v = R.nodes[next];
+            wni = next;
+          }
+        }
+      }
+      shade = has_path && !walking;
+    } else if constexpr (kBvh) {
       // the resumable sphere-BVH walk; the lanes whose walk is done shade
       const int nn = kLdsBvh ? sc->n_lw_nodes : sc->n_nodes;
       if (has_path && wni < 0) {  // a new ray: the quads first (their hit bounds the walk)
@@ -695,7 +737,10 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
     if (shade) {
       f3 emit = mk(0.f, 0.f, 0.f);
       int res;
-      if constexpr (kBvh) {
+      if constexpr (kMesh) {
+        res = shade_hit<false, true, true>(sc, ps, seed, emit, hist + (int64_t)ps.d * stride, D, s_qshade, wh, gdbg);
+        wni = -1;
+      } else if constexpr (kBvh) {
         res = shade_hit<kBvh, true>(sc, ps, seed, emit, hist + (int64_t)ps.d * stride, D, s_qshade, wh,
                                     gdbg);  // (stats build: the region counters; nullptr otherwise)
         wni = -1;
@@ -796,10 +841,12 @@ __device__ __forceinline__ void pool_body(const DevScene* __restrict__ sc, const
 #define RTP_POOL_VGPR_ATTR
 #endif
 template <bool kStats, bool kBvh, bool kTiles = false, bool kPlan = false, bool kSteal = false, bool kViews = false,
-          bool kResume = false>
+          bool kResume = false, bool kMesh = false>
 __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_ATTR
     rtp_render_pool(const DevScene* __restrict__ sc, KParams p, int n_waves) {
   static_assert(!kViews || (!kStats && !kBvh && !kTiles && !kPlan), "batched views: the plain and stealing instances");
+  static_assert(!kMesh || (!kStats && !kBvh && !kTiles && !kPlan && !kViews),
+                "mesh scenes: {plain, stealing} x {render, resume}");
   static_assert(!kResume || (!kStats && !kTiles && !kPlan && !kViews),
                 "resume: {no BVH, global sphere walk} x {plain, stealing}; no stats, wave plan, tile deal or views");
   __shared__ __align__(16) unsigned char smem[pool_lds_bytes(kWavesPerBlock)];
@@ -814,8 +861,8 @@ __global__ void __launch_bounds__(256, RTP_POOL_MIN_WAVES_PER_EU) RTP_POOL_VGPR_
     __shared__ uint32_t entry[kWavesPerBlock * kPool];
     s_entry = entry;
   }
-  pool_body<PoolCfg<kStats, kBvh, kTiles, kPlan, kSteal, kViews, kResume>>(sc, p, n_waves, smem, s_qshade, nullptr,
-                                                                           s_entry, s_m2);
+  pool_body<PoolCfg<kStats, kBvh, kTiles, kPlan, kSteal, kViews, kResume, /*LdsBvh*/ false, kMesh>>(
+      sc, p, n_waves, smem, s_qshade, nullptr, s_entry, s_m2);
 }
 
 // Scenes whose LDS walk tree fits (DevScene::lw_nodes, rtp_lds_walk_capacity):

@@ -234,6 +234,109 @@ RTP_DEV void spheres_bvh(const DevScene* __restrict__ sc, f3 o, f3 d, Hit& h) {
   bvh_resolve(h, R);
 }
 
+// ---------------------------------------------------------- mesh scenes ---
+// Mesh scenes (rtp_set_scene_mesh): the quads lie in global memory in the
+// leaf order of a threaded BVH (rtp_layout.hpp DevScene::mesh_nodes), the
+// spheres (at most kBvhMinSpheres - 1) inline.  The closest hit is the
+// scan's: the minimum of (t, quads before spheres, index in the caller's
+// list).  Every quad runs the general test, quad_hit_masked<0>, on a per-lane
+// copy of its 64-byte scan head (4 x 16-byte loads); the e21 / e23 tail is
+// read from memory only by lanes whose quad is no exact parallelogram and
+// whose alpha + beta > 1.  By the zero-structure argument of rtp_device.hpp
+// the general test equals the kind-specific ones on finite rays.
+// One quad (leaf-order position j) against the closest hit so far; h.kind is
+// -1 (none), 0 (a quad, h.idx its caller's index) or 1 (an inline sphere).
+RTP_DEV void mesh_quad_test(GF4* __restrict__ quads, int j, f3 o, f3 d, Hit& h) {
+  GF4* q = quads + 8 * (int64_t)j;  // DevQuad: 8 x 16 B
+  const f4v hd[4] = {q[0], q[1], q[2], q[3]};
+  QuadGeom G;
+  __builtin_memcpy(&G, hd, sizeof(G));
+  float t;
+  const bool ok = quad_hit_masked<0>(G, *reinterpret_cast<const DevQuad*>((const f4v*)q), o, d, t);
+  const int idx = (int)G.key_lo;
+  if (ok && t > 0.001f && (t < h.t || (t == h.t && (h.kind == 1 || (h.kind == 0 && idx < h.idx))))) {
+    h.t = t;
+    h.kind = 0;
+    h.idx = idx;
+  }
+}
+// the inline spheres of a mesh scene, in index order with a strict '<': the
+// start of a ray's search (a quad at the same t wins in mesh_quad_test)
+RTP_DEV Hit mesh_spheres(const DevScene* __restrict__ sc, f3 o, f3 d) {
+  Hit h{3.40282347e+38f, -1, 0};
+  const int ns = sc->n_spheres;
+  for (int k = 0; k < ns; k++) {
+    const DevSphere& S = sc->spheres[k];
+    float t;
+    if (sphere_hit(o, d, 0.001f, h.t, ld3(S.c), S.rr, t)) {
+      h.t = t;
+      h.kind = 1;
+      h.idx = k;
+    }
+  }
+  return h;
+}
+// A ray's view of the mesh BVH: its octant's near-to-far copy and the slab
+// test's constants (BvhRay's).
+struct MeshRay {
+  GU4* nodes;
+  float ix, iy, iz;
+  float ox, oy, oz;
+};
+RTP_DEV MeshRay mesh_ray(const DevScene* __restrict__ sc, f3 o, f3 d) {
+  MeshRay R;
+  R.nodes = (GU4*)(sc->mesh_nodes + 4 * ((int64_t)ray_octant(d) * sc->n_mesh_nodes));
+  R.ix = slab_rcp(d.x);
+  R.iy = slab_rcp(d.y);
+  R.iz = slab_rcp(d.z);
+  R.ox = -(o.x * R.ix);
+  R.oy = -(o.y * R.iy);
+  R.oz = -(o.z * R.iz);
+  return R;
+}
+// One node of the mesh walk (bvh_visit's shape: the same slab test and cull;
+// the boxes are padded on the host, rtp_layout.hpp kMeshCosMin): returns the
+// next node (>= n_mesh_nodes: done).
+RTP_DEV int mesh_visit(GF4* __restrict__ quads, const MeshRay& R, f3 o, f3 d, u4v v, int ni, Hit& h) {
+  const float x0 = __builtin_fmaf(half_lo(v.x), R.ix, R.ox), x1 = __builtin_fmaf(half_hi(v.y), R.ix, R.ox);
+  const float y0 = __builtin_fmaf(half_hi(v.x), R.iy, R.oy), y1 = __builtin_fmaf(half_lo(v.z), R.iy, R.oy);
+  const float z0 = __builtin_fmaf(half_lo(v.y), R.iz, R.oz), z1 = __builtin_fmaf(half_hi(v.z), R.iz, R.oz);
+  const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fminf(z0, z1));
+  const float tf = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fmaxf(z0, z1));
+  const float slack = 1e-5f * fabsf(tf) + 1e-7f;
+  const bool hit = tn <= tf + slack && tf >= 0.0f && tn <= h.t * 1.00001f + 1e-7f;
+  const bool leaf = (v.w & kCBvhLeafBit) != 0;
+  if (hit && leaf) {
+    const int first = (int)((v.w & ~kCBvhLeafBit) >> 3), cnt = (int)(v.w & 7u);
+    for (int j = first; j < first + cnt; j++) mesh_quad_test(quads, j, o, d, h);
+  }
+  return (hit || leaf) ? ni + 1 : (int)v.w;
+}
+// The whole search of one ray (the diagnostics kernels; the pool kernel runs
+// the same steps resumably): kScan: every quad in storage order instead of
+// the walk -- the (t, index) minimum does not depend on the order, so this is
+// the scan in index order with a strict '<'.
+template <bool kScan>
+RTP_DEV Hit closest_hit_mesh(const DevScene* __restrict__ sc, f3 o, f3 d) {
+  Hit h = mesh_spheres(sc, o, d);
+  GF4* __restrict__ quads = (GF4*)sc->mesh_quads;
+  if constexpr (kScan) {
+    const int nq = sc->n_mesh_quads;
+    for (int j = 0; j < nq; j++) mesh_quad_test(quads, j, o, d, h);
+  } else {
+    const MeshRay R = mesh_ray(sc, o, d);
+    const int nn = sc->n_mesh_nodes;
+    int ni = 0;
+    u4v v = R.nodes[0];
+    while (ni < nn) {
+      const int next = mesh_visit(quads, R, o, d, v, ni, h);
+      if (next < nn) v = R.nodes[next];
+      ni = next;
+    }
+  }
+  return h;
+}
+
 // qshade: the block's LDS copy of the quads' shading data (n, alb, mt) so
 // the hit's material is an LDS gather instead of a global one.
 // Every quad of a scene (kMaxQuads, 8 KiB): with a table that could be
@@ -527,7 +630,8 @@ RTP_DEV void dbg_add(unsigned long long* gdbg, int c, unsigned long long v) { at
 // depth-k draws (which + generator, exactly one dead step) to the caller's
 // fast-forward instead of drawing them here.
 // qshade: the block's LDS quad table (fill_qshade).
-template <bool kBvh, bool kDeferDead>
+// kMesh: a mesh scene (a quad hit's record comes from DevScene::mesh_shade).
+template <bool kBvh, bool kDeferDead, bool kMesh = false>
 RTP_DEV int shade_hit(const DevScene* __restrict__ sc, Path& ps, uint32_t& seed, f3& emit, float4* __restrict__ hist_d,
                       int D, const float* qshade, const Hit h, unsigned long long* dbg = nullptr);
 template <bool kBvh, bool kDeferDead = false>
@@ -562,7 +666,7 @@ RTP_DEV int bounce(const DevScene* __restrict__ sc, Path& ps, uint32_t& seed, f3
 // generate, pdfs, scatter (bounce() above; the pool kernel's resumable
 // sphere-BVH walk calls it directly for the lanes whose walk has finished).
 // dbg (stats build only): the wave's global counter record (dbg_region).
-template <bool kBvh, bool kDeferDead>
+template <bool kBvh, bool kDeferDead, bool kMesh>
 RTP_DEV int shade_hit(const DevScene* __restrict__ sc, Path& ps, uint32_t& seed, f3& emit, float4* __restrict__ hist_d,
                       int D, const float* qshade, const Hit h, unsigned long long* dbg) {
   const uint32_t t1 = sc->which_t1, t2 = sc->which_t2;
@@ -578,7 +682,21 @@ RTP_DEV int shade_hit(const DevScene* __restrict__ sc, Path& ps, uint32_t& seed,
   f3 hn;
   int mt;
   f3 alb;
-  if (h.kind == 0) {
+  if constexpr (kMesh) {
+    if (h.kind == 0) {  // a mesh quad: its 32-byte record, a per-lane global gather (h.idx: the caller's index)
+      GF4* r = (GF4*)sc->mesh_shade + 2 * (int64_t)h.idx;
+      const f4v r0 = r[0], r1 = r[1];
+      hn = mk(r0.x, r0.y, r0.z);
+      alb = mk(r0.w, r1.x, r1.y);
+      mt = __float_as_int(r1.z);
+      if (dot(hn, dir) > 0.f) hn = neg(hn);  // Surface.h:184-185
+    } else {
+      const DevSphere& S = sc->spheres[h.idx];
+      hn = mk((hp.x - S.c[0]) / S.r, (hp.y - S.c[1]) / S.r, (hp.z - S.c[2]) / S.r);
+      mt = S.mt;
+      alb = ld3(S.alb);
+    }
+  } else if (h.kind == 0) {
     // (an LDS table always: a global fallback here made the compiler read
     // both through one flat pointer)
     const float4* r = reinterpret_cast<const float4*>(qshade + h.idx * kQShadeFloats);  // 16-byte aligned

@@ -89,6 +89,23 @@ class Device:
                                 sphere_tex, mat_type, tex_type, tex, light_quad_points, light_sphere_point, ior)
         check(self._L.rtp_set_scene(self.handle, d))
 
+    def set_scene_mesh(self, coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius, sphere_mat,
+                       sphere_tex, mat_type, tex_type, tex, light_quad_points=(8, 9, 10, 11), light_sphere_point=48,
+                       ior=1.5):
+        """rtp_set_scene_mesh: set_scene's arguments, any number of quads up to
+        2^22 behind a BVH in device memory, at most 8 spheres."""
+        d, _arrays = scene_desc(coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius, sphere_mat,
+                                sphere_tex, mat_type, tex_type, tex, light_quad_points, light_sphere_point, ior)
+        check(self._L.rtp_set_scene_mesh(self.handle, d))
+
+    def mesh_guarantee(self) -> tuple[float, float]:
+        """(cos_min, reach) of the current mesh scene (rtp_mesh_guarantee): the
+        walk equals the scan of every quad for rays from within ``reach`` of
+        the hit quad that meet its plane with |cos| >= ``cos_min``."""
+        cm, rc = ctypes.c_float(), ctypes.c_float()
+        check(self._L.rtp_mesh_guarantee(self.handle, cm, rc))
+        return float(cm.value), float(rc.value)
+
     def set_cornell_box(self, variant: int = 0):
         d = RtpSceneDesc()
         check(self._L.rtp_cornell_box(variant, d))

@@ -214,8 +214,26 @@ def _set_scene(dev: Device, cellset: CellSet, coords, matIdx, texIdx, matType, t
     radii = cellset.sphere_radius
     if radii is None:
         radii = np.full(len(cellset.sphere_points), np.float32(90 / 555.0), dtype=np.float32)  # extract(), :182
-    dev.set_scene(coords, cellset.quad_points, matIdx[0], texIdx[0], cellset.sphere_points, radii, matIdx[1],
-                  texIdx[1], matType, texType, tex, light_quad_points, light_sphere_point, ior)
+    # more than 256 distinct quads (rtp_set_scene's inline limit): a mesh scene, the quads behind a BVH
+    setter = dev.set_scene_mesh if _distinct_quads(coords, cellset.quad_points, matIdx[0], texIdx[0]) > 256 \
+        else dev.set_scene
+    setter(coords, cellset.quad_points, matIdx[0], texIdx[0], cellset.sphere_points, radii, matIdx[1],
+           texIdx[1], matType, texType, tex, light_quad_points, light_sphere_point, ior)
+
+
+def _distinct_quads(coords, quad_points, quad_mat, quad_tex) -> int:
+    """Quads that differ from every earlier one in a vertex (bit for bit, in
+    order), the material or the texture: what rtp_set_scene keeps."""
+    qp = np.asarray(quad_points, dtype=np.int64).reshape(-1, 4)
+    if len(qp) <= 256:
+        return len(qp)
+    pts = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3).view(np.uint32)
+    if qp.min() < 0 or qp.max() >= len(pts):
+        return len(qp)  # (the library reports the bad id)
+    key = np.concatenate([pts[qp].reshape(len(qp), 12).astype(np.int64),
+                          np.asarray(quad_mat, dtype=np.int64).reshape(-1, 1),
+                          np.asarray(quad_tex, dtype=np.int64).reshape(-1, 1)], axis=1)
+    return len(np.unique(key, axis=0))
 
 
 def _cells_with_radii(cb: CornellBox) -> CellSet:

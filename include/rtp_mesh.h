@@ -46,6 +46,28 @@ extern "C" {
 rtp_status rtp_set_scene_mesh(rtp_context* ctx, const rtp_scene_desc* scene);
 rtp_status rtp_mesh_guarantee(rtp_context* ctx, float* cos_min, float* reach);
 
+/* The same scene from arrays that already live on the context's device, for
+ * cell sets a simulation moves every time step: `points`, `quad_points`,
+ * `quad_mat` and `quad_tex` of the descriptor are DEVICE pointers; everything
+ * else (the spheres' arrays, mat_type, tex_type, tex_rgb, the light ids, ior)
+ * is host memory as before.  Limits, checks and messages are those of
+ * rtp_set_scene_mesh -- the per-quad checks run on the device, and the first
+ * failure by quad index decides the message -- and a refused call leaves the
+ * previous scene in place and rendering.  The BVH (a linear BVH over the
+ * quads' Morton codes), the quad records and the boxes are built on the
+ * device; the host reads back the at most 13 points the spheres and lights
+ * name, one 64-byte record and the node count, nothing that grows with the
+ * mesh.  The work is enqueued on `hip_stream` (NULL: the null stream), behind
+ * whatever the caller queued there to produce the arrays, and the call
+ * returns once the scene is in place: it synchronises that stream.  The
+ * caller's arrays are not kept.  The closest hit, the promise and
+ * rtp_mesh_guarantee (the same cos_min and reach, bit for bit) are those of
+ * rtp_set_scene_mesh for the same scene, and so is every pixel; only the
+ * tree, and with it the walk's speed, differs.  RTP_MESH_SCAN=1 is honoured.
+ * RTP_MESH_BUILD=gpu makes rtp_set_scene_mesh upload its host arrays and take
+ * this path (the A/B handle); unset or `host`, it builds on the host. */
+rtp_status rtp_set_scene_mesh_device(rtp_context* ctx, const rtp_scene_desc* scene, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

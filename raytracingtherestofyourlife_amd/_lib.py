@@ -154,6 +154,7 @@ EXPORTED_SYMBOLS = list(SIGNATURES)
 MESH_SIGNATURES = {
     "rtp_set_scene_mesh": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc)]),
     "rtp_mesh_guarantee": (ctypes.c_int32, [vp, f32p, f32p]),
+    "rtp_set_scene_mesh_device": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc), vp]),
 }
 
 

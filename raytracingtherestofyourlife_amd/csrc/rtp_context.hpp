@@ -40,6 +40,13 @@ struct rtp_context {
   rtp::DevQuad* d_mesh_quads = nullptr;
   float* d_mesh_shade = nullptr;
   float mesh_reach = 0.f;
+  // for rtp_debug_mesh_readback: the tree's size, and each quad's padded box
+  // (6 floats) and pad in the caller's order -- on the device after the device
+  // build (rtp_set_scene_mesh_device), on the host after the host build
+  int32_t n_mesh_nodes = 0, n_mesh_quads = 0;
+  float* d_mesh_boxes = nullptr;
+  float* d_mesh_pads = nullptr;
+  std::vector<float> h_mesh_boxes, h_mesh_pads;
   int oct_mask = 0;  // the global walk's octant mask (DevScene::oct_mask) of the current scene
   int ff_policy = 0;  // rtp_ff_policy (RNG jump tables)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -26,6 +26,7 @@
 #include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_mesh.hpp"
+#include "rtp_mesh_gpu.hpp"
 
 extern "C" const char* rtp_instance_name(int variant, int stats, int walk, int tiles, int plan, int steal, int views,
                                          int resume);
@@ -488,8 +489,8 @@ void rtp_destroy(rtp_context* c) {
   for (void* p : {(void*)c->d_scene, (void*)c->d_hist, (void*)c->d_dbg, (void*)c->d_progress, (void*)c->d_nodes,
                   (void*)c->d_sph_geom, (void*)c->d_sph_all, (void*)c->d_lw_nodes, (void*)c->d_lw_cidx,
                   (void*)c->d_lw_sph, (void*)c->d_lw_orig, (void*)c->d_cnodes, (void*)c->d_cidx, (void*)c->d_direct,
-                  (void*)c->d_mesh_nodes, (void*)c->d_mesh_quads, (void*)c->d_mesh_shade, c->d_adapt_sel,
-                  c->d_adapt_state})
+                  (void*)c->d_mesh_nodes, (void*)c->d_mesh_quads, (void*)c->d_mesh_shade, (void*)c->d_mesh_boxes,
+                  (void*)c->d_mesh_pads, c->d_adapt_sel, c->d_adapt_state})
     if (p) (void)hipFree(p);
   for (hipEvent_t e : {c->ev0, c->ev1, c->done})
     if (e) (void)hipEventDestroy(e);
@@ -529,6 +530,9 @@ struct SceneBuild {
   std::vector<uint32_t> mesh_cnodes;       // 8 * n_nodes compact nodes
   std::vector<rtp::DevQuad> mesh_quads;    // leaf order
   std::vector<float> mesh_shade;           // 8 floats per quad, the caller's order
+  // or, built on the device (rtp_mesh_gpu.hip): the arrays themselves, which scene_upload adopts
+  bool mesh_on_device = false;
+  rtp::MeshGpuOut mesh_dev;
 };
 
 // (pt_ok, mat_ok, tex_ok: rtp_host_util.hpp, shared with the mesh builder)
@@ -892,7 +896,7 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
   for (void** p : {(void**)&c->d_nodes, (void**)&c->d_sph_geom, (void**)&c->d_sph_all, (void**)&c->d_cnodes,
                    (void**)&c->d_cidx, (void**)&c->d_lw_nodes, (void**)&c->d_lw_cidx, (void**)&c->d_lw_sph,
                    (void**)&c->d_lw_orig, (void**)&c->d_mesh_nodes, (void**)&c->d_mesh_quads,
-                   (void**)&c->d_mesh_shade})
+                   (void**)&c->d_mesh_shade, (void**)&c->d_mesh_boxes, (void**)&c->d_mesh_pads})
     if (*p) {
       const hipError_t e = hipFree(*p);
       *p = nullptr;
@@ -911,7 +915,22 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
     h->cnodes = c->d_cnodes;
     h->cidx = c->d_cidx;
   }
-  if (B.mesh) {
+  c->h_mesh_boxes.clear();
+  c->h_mesh_pads.clear();
+  if (B.mesh && B.mesh_on_device) {
+    // built in place while the previous scene was still whole: from here on the arrays are the context's
+    c->d_mesh_nodes = B.mesh_dev.nodes;
+    c->d_mesh_quads = B.mesh_dev.quads;
+    c->d_mesh_shade = B.mesh_dev.shade;
+    c->d_mesh_boxes = B.mesh_dev.boxes;
+    c->d_mesh_pads = B.mesh_dev.pads;
+    B.mesh_dev = rtp::MeshGpuOut();
+    h->mesh_nodes = c->d_mesh_nodes;
+    h->mesh_quads = c->d_mesh_quads;
+    h->mesh_shade = c->d_mesh_shade;
+  } else if (B.mesh) {
+    c->h_mesh_boxes = std::move(B.mb.boxes);
+    c->h_mesh_pads = std::move(B.mb.pads);
     const size_t nb = B.mesh_cnodes.size() * 4, qb = B.mesh_quads.size() * sizeof(rtp::DevQuad),
                  sb = B.mesh_shade.size() * 4;
     UPLOAD_TRY(hipMalloc(&c->d_mesh_nodes, nb));
@@ -927,6 +946,8 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
   UPLOAD_TRY(hipMemcpy(c->d_scene, h, sizeof(*h), hipMemcpyHostToDevice));
   c->is_mesh = B.mesh;
   c->mesh_reach = B.mesh ? B.mb.reach : 0.f;
+  c->n_mesh_nodes = B.mesh ? h->n_mesh_nodes : 0;
+  c->n_mesh_quads = B.mesh ? h->n_mesh_quads : 0;
   c->lw_bytes = h->n_lw_nodes > 0 ? 16 * (8 * h->n_lw_nodes + h->n_lw_sph) : 0;
   c->use_bvh = B.use_bvh;
   c->oct_mask = B.use_bvh ? h->oct_mask : 0;
@@ -935,6 +956,109 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
   for (int k = 0; k < 3; k++) c->quad_lo[k] = B.blo[k], c->quad_hi[k] = B.bhi[k];
   c->has_scene = true;
   return RTP_OK;
+}
+// A mesh scene built on the device (include/rtp_mesh.h rtp_set_scene_mesh_device;
+// rtp_mesh_gpu.hip): s->points and s->quad_* are device arrays.  The host
+// reads back one record (the first failed check, the vertices' bounds), the
+// at most 13 points the spheres and lights name, and the node count.  Every
+// check, and the whole build, comes before scene_upload frees anything: a
+// refused or failed call leaves the previous scene rendering.
+rtp_status set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, hipStream_t stream) {
+  RTP_TRY(mesh_validate_head(s));
+  if (!s->quad_points || !s->quad_mat || !s->quad_tex)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh_device: NULL device array");
+  UPLOAD_TRY(hipSetDevice(c->device));
+  // the small tables, as the device's checks and records read them (rtp::MeshGpuIn)
+  const int n_mat = std::max(s->n_mat, 0), n_tt = std::max(s->n_tex_type, 0), n_tex = std::max(s->n_tex, 0);
+  std::vector<int32_t> tab((size_t)n_mat + n_tt + 1);
+  for (int m = 0; m < n_mat; m++) tab[m] = s->mat_type[m] >= 0 && s->mat_type[m] <= 2 ? s->mat_type[m] : -1;
+  for (int t = 0; t < n_tt; t++) tab[n_mat + t] = s->tex_type[t] >= 0 && s->tex_type[t] < s->n_tex ? s->tex_type[t] : -1;
+  const std::vector<float> no_rgb(3, 0.f);
+  DevBufs tmp;
+  int32_t* d_tab = nullptr;
+  float* d_rgb = nullptr;
+  UPLOAD_TRY(tmp.get(&d_tab, tab.size() * sizeof(int32_t), tab.data()));
+  UPLOAD_TRY(tmp.get(&d_rgb, (size_t)std::max(n_tex, 1) * 3 * sizeof(float), n_tex ? s->tex_rgb : no_rgb.data()));
+  rtp::MeshGpuIn in{s->points, s->n_points, s->quad_points, s->quad_mat, s->quad_tex, s->n_quads,
+                    d_tab,     n_mat,       d_tab + n_mat,  n_tt,        d_rgb};
+  rtp::MeshGpuInfo info;
+  UPLOAD_TRY(rtp_mesh_gpu_validate(&in, &info, stream));
+  if (info.first_fail != rtp::kMeshNoFail) return mesh_quad_fail((int)(info.first_fail & 3u));
+  RTP_TRY(mesh_validate_tail(s));
+  // the points the spheres and the lights name, under ids of their own
+  const int ns = s->n_spheres;
+  float pts[3 * 13];
+  int32_t sphere_point[8];
+  rtp_scene_desc hs = *s;
+  auto fetch = [&](int slot, int32_t id) {
+    return hipMemcpyAsync(pts + 3 * slot, s->points + 3 * (size_t)id, 12, hipMemcpyDeviceToHost, stream);
+  };
+  for (int k = 0; k < ns; k++) {
+    UPLOAD_TRY(fetch(k, s->sphere_point[k]));
+    sphere_point[k] = k;
+  }
+  for (int k = 0; k < 4; k++) {
+    UPLOAD_TRY(fetch(ns + k, s->light_quad_points[k]));
+    hs.light_quad_points[k] = ns + k;
+  }
+  UPLOAD_TRY(fetch(ns + 4, s->light_sphere_point));
+  hs.light_sphere_point = ns + 4;
+  UPLOAD_TRY(hipStreamSynchronize(stream));
+  hs.points = pts;
+  hs.n_points = ns + 5;
+  hs.sphere_point = sphere_point;
+  hs.quad_points = hs.quad_mat = hs.quad_tex = nullptr;
+  // the reach: mesh_build's expression over the device's exact min / max and the spheres' c -+ r
+  SceneBuild B;
+  B.mesh = true;
+  {
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; k++) lo[k] = rtp::mesh_key_float(info.lo[k]), hi[k] = rtp::mesh_key_float(info.hi[k]);
+    for (int j = 0; j < ns; j++)
+      for (int k = 0; k < 3; k++) {
+        const float cc = pts[3 * j + k], r = s->sphere_radius[j];
+        lo[k] = std::min(lo[k], cc - r), hi[k] = std::max(hi[k], cc + r);
+      }
+    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
+    B.mb.reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
+    if (!std::isfinite(B.mb.reach)) return mesh_bounds_fail();
+  }
+  rtp::DevScene* h = B.h.get();
+  std::memset(h, 0, sizeof(*h));
+  h->oct_mask = 7;
+  RTP_TRY(scene_spheres(&hs, B));
+  scene_sphere_bvh(&hs, B);
+  RTP_TRY(scene_lights(&hs, B));
+  int32_t open_tree = 0;
+  UPLOAD_TRY(rtp_mesh_gpu_build(&in, B.mb.reach, &B.mesh_dev, &open_tree, stream));
+  if (open_tree) return fail(RTP_ERR_DEVICE, "rtp_set_scene_mesh_device: the radix tree did not close");
+  B.mesh_on_device = true;
+  h->n_mesh_nodes = B.mesh_dev.n_nodes;
+  h->n_mesh_quads = s->n_quads;
+  h->mesh_scan = env_is("RTP_MESH_SCAN", '1') ? 1 : 0;
+  for (int k = 0; k < 3; k++) B.blo[k] = 0.f, B.bhi[k] = 0.f;
+  const rtp_status rs = scene_upload(c, s, B);
+  rtp_mesh_gpu_free(&B.mesh_dev);  // (what scene_upload did not get to adopt)
+  return rs;
+}
+
+// RTP_MESH_BUILD=gpu on rtp_set_scene_mesh: its four host arrays go up and the device build runs
+rtp_status set_scene_mesh_uploaded(rtp_context* c, const rtp_scene_desc* s) {
+  RTP_TRY(mesh_validate_head(s));
+  if (!s->quad_points || !s->quad_mat || !s->quad_tex)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh: NULL argument");
+  UPLOAD_TRY(hipSetDevice(c->device));
+  DevBufs tmp;
+  rtp_scene_desc ds = *s;
+  float* d_points = nullptr;
+  int32_t *d_qp = nullptr, *d_qm = nullptr, *d_qt = nullptr;
+  const size_t n = (size_t)s->n_quads;
+  UPLOAD_TRY(tmp.get(&d_points, (size_t)s->n_points * 12, s->points));
+  UPLOAD_TRY(tmp.get(&d_qp, n * 16, s->quad_points));
+  UPLOAD_TRY(tmp.get(&d_qm, n * 4, s->quad_mat));
+  UPLOAD_TRY(tmp.get(&d_qt, n * 4, s->quad_tex));
+  ds.points = d_points, ds.quad_points = d_qp, ds.quad_mat = d_qm, ds.quad_tex = d_qt;
+  return set_scene_mesh_device(c, &ds, nullptr);
 }
 #undef UPLOAD_TRY
 
@@ -958,6 +1082,9 @@ rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
 // refusal comes before the upload: the previous scene stays.
 rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
   if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh: NULL argument");
+  // RTP_MESH_BUILD=gpu: the device build from these host arrays (the A/B handle, like RTP_BVH_BUILD)
+  if (const char* mb = getenv("RTP_MESH_BUILD"))
+    if (!std::strcmp(mb, "gpu")) return set_scene_mesh_uploaded(c, s);
   SceneBuild B;
   B.mesh = true;
   RTP_TRY(mesh_build(s, B.mb));
@@ -992,6 +1119,39 @@ rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
   h->mesh_scan = env_is("RTP_MESH_SCAN", '1') ? 1 : 0;
   for (int k = 0; k < 3; k++) B.blo[k] = 0.f, B.bhi[k] = 0.f;  // (-direct mode is refused on a mesh scene)
   return scene_upload(c, s, B);
+}
+
+rtp_status rtp_set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, void* hip_stream) {
+  if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh_device: NULL argument");
+  return set_scene_mesh_device(c, s, static_cast<hipStream_t>(hip_stream));
+}
+
+// test hook (rtp_mesh.hpp): the current mesh scene as its builder left it
+rtp_status rtp_debug_mesh_readback(rtp_context* c, int32_t oct, int32_t node_cap, int32_t* n_nodes, void* cnodes,
+                                   int32_t* order, float* boxes, float* pads) {
+  if (!c || !c->has_scene || !c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: the context holds no mesh scene");
+  if (oct < 0 || oct > 7) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: octant outside 0..7");
+  HIP_TRY(hipSetDevice(c->device));
+  RTP_TRY(drain(c));
+  const size_t nn = (size_t)c->n_mesh_nodes, nq = (size_t)c->n_mesh_quads;
+  if (n_nodes) *n_nodes = c->n_mesh_nodes;
+  if (cnodes) {
+    if (node_cap < c->n_mesh_nodes)
+      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: node_cap too small");
+    HIP_TRY(hipMemcpy(cnodes, c->d_mesh_nodes + 4 * nn * (size_t)oct, 16 * nn, hipMemcpyDeviceToHost));
+  }
+  if (order)
+    HIP_TRY(hipMemcpy2D(order, sizeof(int32_t), reinterpret_cast<const char*>(c->d_mesh_quads) + offsetof(rtp::DevQuad, orig),
+                        sizeof(rtp::DevQuad), sizeof(int32_t), nq, hipMemcpyDeviceToHost));
+  if (c->d_mesh_boxes) {
+    HIP_TRY(DevBufs::back(boxes, c->d_mesh_boxes, 24 * nq));
+    HIP_TRY(DevBufs::back(pads, c->d_mesh_pads, 4 * nq));
+  } else {
+    if (boxes) std::memcpy(boxes, c->h_mesh_boxes.data(), 24 * nq);
+    if (pads) std::memcpy(pads, c->h_mesh_pads.data(), 4 * nq);
+  }
+  return RTP_OK;
 }
 
 rtp_status rtp_mesh_guarantee(rtp_context* c, float* cos_min, float* reach) {

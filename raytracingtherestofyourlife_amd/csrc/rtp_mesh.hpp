@@ -20,6 +20,14 @@ struct MeshBuild {
 
 // the descriptor checks of rtp_set_scene_mesh (rtp_set_scene's, and the mesh scene's counts)
 rtp_status mesh_validate(const rtp_scene_desc* s);
+// its parts, for the device build (rtp_set_scene_mesh_device), which makes the
+// per-quad checks on the device: the counts; the message of the per-quad check
+// that failed (0 point id, 1 material / texture, 2 vertex not finite); the
+// spheres and lights; and mesh_build's refusal of bounds that are not finite
+rtp_status mesh_validate_head(const rtp_scene_desc* s);
+rtp_status mesh_quad_fail(int check);
+rtp_status mesh_validate_tail(const rtp_scene_desc* s);
+rtp_status mesh_bounds_fail();
 // validate, pad, build (binned SAH, leaves of <= leaf_size quads) and thread the 8 octant copies
 rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& out, int leaf_size = rtp::kMeshLeaf);
 // BvhNodes -> the walk's 16-byte compact nodes (half-precision boxes rounded outward)
@@ -42,4 +50,11 @@ extern "C" rtp_status rtp_mesh_build_host(const rtp_scene_desc* scene, int32_t o
 extern "C" int32_t rtp_mesh_leaf_size(void);
 extern "C" void rtp_mesh_compact_host(const void* nodes, int64_t n, uint32_t* out);
 extern "C" rtp_status rtp_mesh_scan_host(const rtp_scene_desc* scene, const float* rays, int64_t n, uint32_t* out);
+// The context's current mesh scene as its builder left it, host or device
+// (rtp_host.cpp): octant `oct`'s compact nodes (16 bytes each, at most
+// node_cap), the leaf order (DevQuad::orig of each stored quad), and each
+// quad's padded box (6 floats) and pad in the caller's order.  Every output is
+// optional.
+extern "C" rtp_status rtp_debug_mesh_readback(rtp_context* ctx, int32_t oct, int32_t node_cap, int32_t* n_nodes,
+                                              void* cnodes, int32_t* order, float* boxes, float* pads);
 

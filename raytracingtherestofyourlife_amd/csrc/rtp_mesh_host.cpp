@@ -84,7 +84,7 @@ uint32_t half_outward(float x, bool up) {
 }
 }  // namespace
 
-rtp_status mesh_validate(const rtp_scene_desc* s) {
+rtp_status mesh_validate_head(const rtp_scene_desc* s) {
   if (!s) return bad("rtp_set_scene_mesh: NULL argument");
   if (s->n_points <= 0 || !s->points) return bad("rtp_set_scene: no points");
   if (s->n_quads < 0 || s->n_spheres < 0) return bad("rtp_set_scene: bad primitive counts");
@@ -93,16 +93,16 @@ rtp_status mesh_validate(const rtp_scene_desc* s) {
     return bad("rtp_set_scene_mesh: a mesh scene takes 1 to 4194304 quads");
   if (s->n_spheres >= rtp::kBvhMinSpheres)
     return bad("rtp_set_scene_mesh: a mesh scene takes at most 8 spheres (no quad BVH together with a sphere BVH)");
-  for (int q = 0; q < s->n_quads; q++) {
-    for (int k = 0; k < 4; k++)
-      if (!pt_ok(s, s->quad_points[4 * q + k])) return bad("rtp_set_scene: quad point id out of range");
-    if (!mat_ok(s, s->quad_mat[q]) || !tex_ok(s, s->quad_tex[q]))
-      return bad("rtp_set_scene: quad material/texture index out of range");
-    for (int k = 0; k < 4; k++)
-      for (int a = 0; a < 3; a++)
-        if (!std::isfinite(s->points[3 * s->quad_points[4 * q + k] + a]))
-          return bad("rtp_set_scene_mesh: a quad vertex is not finite");
-  }
+  return RTP_OK;
+}
+
+rtp_status mesh_quad_fail(int check) {
+  return bad(check == 0   ? "rtp_set_scene: quad point id out of range"
+             : check == 1 ? "rtp_set_scene: quad material/texture index out of range"
+                          : "rtp_set_scene_mesh: a quad vertex is not finite");
+}
+
+rtp_status mesh_validate_tail(const rtp_scene_desc* s) {
   for (int k = 0; k < s->n_spheres; k++)
     if (!pt_ok(s, s->sphere_point[k]) || !mat_ok(s, s->sphere_mat[k]) || !tex_ok(s, s->sphere_tex[k]) ||
         !(s->sphere_radius[k] > 0.0f))
@@ -111,6 +111,22 @@ rtp_status mesh_validate(const rtp_scene_desc* s) {
     if (!pt_ok(s, s->light_quad_points[k])) return bad("rtp_set_scene: light quad point id out of range");
   if (!pt_ok(s, s->light_sphere_point)) return bad("rtp_set_scene: light sphere point id out of range");
   return RTP_OK;
+}
+
+rtp_status mesh_bounds_fail() { return bad("rtp_set_scene_mesh: the scene's bounds are not finite"); }
+
+rtp_status mesh_validate(const rtp_scene_desc* s) {
+  const rtp_status rs = mesh_validate_head(s);
+  if (rs != RTP_OK) return rs;
+  for (int q = 0; q < s->n_quads; q++) {
+    for (int k = 0; k < 4; k++)
+      if (!pt_ok(s, s->quad_points[4 * q + k])) return mesh_quad_fail(0);
+    if (!mat_ok(s, s->quad_mat[q]) || !tex_ok(s, s->quad_tex[q])) return mesh_quad_fail(1);
+    for (int k = 0; k < 4; k++)
+      for (int a = 0; a < 3; a++)
+        if (!std::isfinite(s->points[3 * s->quad_points[4 * q + k] + a])) return mesh_quad_fail(2);
+  }
+  return mesh_validate_tail(s);
 }
 
 rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
@@ -133,7 +149,7 @@ rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
     }
   const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
   B.reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
-  if (!std::isfinite(B.reach)) return bad("rtp_set_scene_mesh: the scene's bounds are not finite");
+  if (!std::isfinite(B.reach)) return mesh_bounds_fail();
   B.boxes.resize((size_t)6 * n);
   B.pads.resize(n);
   std::vector<BvhPrim> P(n);

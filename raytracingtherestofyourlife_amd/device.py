@@ -98,6 +98,47 @@ class Device:
                                 sphere_tex, mat_type, tex_type, tex, light_quad_points, light_sphere_point, ior)
         check(self._L.rtp_set_scene_mesh(self.handle, d))
 
+    def set_scene_mesh_device(self, coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius, sphere_mat,
+                              sphere_tex, mat_type, tex_type, tex, light_quad_points=(8, 9, 10, 11),
+                              light_sphere_point=48, ior=1.5, stream=None):
+        """rtp_set_scene_mesh_device: the mesh scene of set_scene_mesh from
+        tensors that live on this device's GPU -- coords float32 [P, 3],
+        quad_points int32 [Q, 4], quad_mat and quad_tex int32 [Q], contiguous
+        -- with the BVH built there.  The other arguments are host arrays as
+        for set_scene_mesh.  ``stream``: a torch stream or a raw hipStream_t
+        (None: torch's current stream on this device); the build is queued
+        behind the work that produced the tensors there, and the call returns
+        when the scene is in place.  The tensors are not kept."""
+        import torch
+
+        want = (("coords", coords, torch.float32, (None, 3)), ("quad_points", quad_points, torch.int32, (None, 4)),
+                ("quad_mat", quad_mat, torch.int32, (None,)), ("quad_tex", quad_tex, torch.int32, (None,)))
+        for name, t, dtype, shape in want:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device.index != self.device:
+                raise ValueError(f"set_scene_mesh_device: {name} must be a CUDA tensor on device {self.device}")
+            if t.dtype != dtype or t.dim() != len(shape) or any(s is not None and t.shape[i] != s
+                                                                 for i, s in enumerate(shape)):
+                raise ValueError(f"set_scene_mesh_device: {name} must be {dtype} of shape "
+                                 f"[{', '.join('N' if s is None else str(s) for s in shape)}]")
+            if not t.is_contiguous():
+                raise ValueError(f"set_scene_mesh_device: {name} must be contiguous")
+        if not (quad_points.shape[0] == quad_mat.shape[0] == quad_tex.shape[0]):
+            raise ValueError("set_scene_mesh_device: quad_points, quad_mat and quad_tex differ in length")
+        none = np.zeros(0, dtype=np.int32)
+        d, _arrays = scene_desc(np.zeros(0, dtype=np.float32), none, none, none, sphere_points, sphere_radius,
+                                sphere_mat, sphere_tex, mat_type, tex_type, tex, light_quad_points,
+                                light_sphere_point, ior)
+        d.points = ctypes.cast(coords.data_ptr(), _lib.f32p)
+        d.n_points = coords.shape[0]
+        d.quad_points = ctypes.cast(quad_points.data_ptr(), _lib.i32p)
+        d.quad_mat = ctypes.cast(quad_mat.data_ptr(), _lib.i32p)
+        d.quad_tex = ctypes.cast(quad_tex.data_ptr(), _lib.i32p)
+        d.n_quads = quad_points.shape[0]
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+        check(self._L.rtp_set_scene_mesh_device(self.handle, d, handle))
+
     def mesh_guarantee(self) -> tuple[float, float]:
         """(cos_min, reach) of the current mesh scene (rtp_mesh_guarantee): the
         walk equals the scan of every quad for rays from within ``reach`` of

@@ -1,0 +1,514 @@
+"""The device build of a mesh scene's quad BVH (rtp_set_scene_mesh_device):
+vertices and connectivity as torch tensors on the GPU, the linear BVH, the quad
+records and the boxes built there.  Held to the host build of the same scene:
+pads, boxes and the guarantee bit for bit; the tree's structure in all 8
+octant copies, read back and walked on the host; the gathered records (the
+device's brute-force scan, ray by ray); the walk against the scan inside the
+promise; pixels against the host-built scene, the live oracle and the goldens;
+the smallest shapes at which the build can go wrong; refusals with the host
+call's messages; time steps on moving vertices; and RTP_MESH_BUILD=gpu."""
+from __future__ import annotations
+
+import ctypes
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import _meshes
+import _scenes
+from _adaptive_ref import active_ref, noise_ref
+from _util import assert_render_equal
+
+pytestmark = pytest.mark.gpu
+
+F, U = np.float32, np.uint32
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MAX_OUTSIDE = 0.01
+SCENES = ("tess", "facets", "bent")
+HUGE = F(2.0 ** 100)
+LEAF_BIT = 0x40000000
+NX, NY, SPP, DEPTH = 24, 16, 4, 8
+CAMS = {"default": None, "high": _scenes.HIGH_CAM}
+
+
+@pytest.fixture(scope="module")
+def rtp():
+    import raytracingtherestofyourlife_amd as rtp
+
+    return rtp
+
+
+@pytest.fixture(autouse=True)
+def _leave_the_cornell_box(device):
+    yield
+    device.set_cornell_box(0)
+
+
+def _mesh(name):
+    return _meshes.grid(name) if isinstance(name, int) else _meshes.SCENES[name]() if name in _meshes.SCENES \
+        else _meshes.cornell(int(name[-1]))
+
+
+@functools.lru_cache(maxsize=None)
+def _host(name):
+    return _meshes.build_host(_mesh(name))
+
+
+def _pad(name):
+    pads = _host(name)["pads"]
+    return float(np.median(pads[pads < 2.0 ** 99]))
+
+
+def _tensors(m, coords=None):
+    import torch
+
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(device="cuda", dtype=dt)
+    return (t(m.points, torch.float32) if coords is None else coords, t(m.quads, torch.int32),
+            t(m.quad_mat, torch.int32), t(m.quad_tex, torch.int32))
+
+
+def _set_dev(device, m, coords=None, stream=None):
+    import torch
+
+    if stream is not None:  # (the connectivity tensors are made on the current stream)
+        stream.wait_stream(torch.cuda.current_stream())
+    device.set_scene_mesh_device(*_tensors(m, coords), *m.set_args()[4:], stream=stream)
+    return device.mesh_guarantee()
+
+
+def _set_host(device, m):
+    device.set_scene_mesh(*m.set_args())
+    return device.mesh_guarantee()
+
+
+def _readback(device, nq, oct=0):
+    """rtp_debug_mesh_readback: dict(cnodes uint32 [n, 4], order, boxes, pads) of the current mesh scene."""
+    L = device._L
+    fn = L.rtp_debug_mesh_readback
+    fn.restype = ctypes.c_int32
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5
+    cn = np.zeros((2 * nq, 4), dtype=U)
+    order = np.full(nq, -1, dtype=np.int32)
+    boxes = np.zeros((nq, 6), dtype=F)
+    pads = np.zeros(nq, dtype=F)
+    nn = ctypes.c_int32(0)
+    rc = fn(device.handle, oct, len(cn), ctypes.addressof(nn), cn.ctypes.data, order.ctypes.data, boxes.ctypes.data,
+            pads.ctypes.data)
+    assert rc == 0, L.rtp_last_error()
+    return dict(cnodes=cn[: nn.value].copy(), order=order, boxes=boxes, pads=pads)
+
+
+def _half_boxes(cn):
+    """The decoded half-precision boxes of compact nodes: (lo, hi) float32 [n, 3]."""
+    h = np.ascontiguousarray(cn[:, :3]).view(np.float16).astype(F)  # lo.x lo.y | lo.z hi.x | hi.y hi.z
+    return h[:, :3], h[:, 3:]
+
+
+def _check_structure(device, m, leaf_size):
+    """Every octant copy of the current scene's tree, walked on the host."""
+    nq = len(m.quads)
+    leaves = None
+    for oct in range(8):
+        r = _readback(device, nq, oct)
+        cn, order, boxes, pads = r["cnodes"], r["order"], r["boxes"], r["pads"]
+        n = len(cn)
+        assert n >= 1
+        assert np.array_equal(np.sort(order), np.arange(nq)), "the leaf order is a permutation of the quads"
+        lo, hi = _half_boxes(cn)
+        w = cn[:, 3]
+        leaf = (w & LEAF_BIT) != 0
+        seen = np.zeros(nq, dtype=np.int32)
+        stack = []  # (end, lo, hi) of the open inner nodes
+        for i in range(n):
+            while stack and stack[-1][0] == i:
+                stack.pop()
+            end = i + 1 if leaf[i] else int(w[i])
+            assert i < end <= n, (oct, i, end)
+            if stack:
+                pend, plo, phi = stack[-1]
+                assert end <= pend, f"octant {oct}: node {i}'s span [{i}, {end}) leaves its parent's (ends at {pend})"
+                assert (lo[i] >= plo).all() and (hi[i] <= phi).all(), f"octant {oct}: node {i}'s box leaves its parent's"
+            else:
+                assert i == 0 and end == n, f"octant {oct}: node {i} is outside the root's span"
+            if leaf[i]:
+                first, count = int(w[i] & ~U(LEAF_BIT)) >> 3, int(w[i] & 7)
+                assert 1 <= count <= leaf_size and first + count <= nq, (oct, i, first, count)
+                q = order[first:first + count]
+                seen[first:first + count] += 1
+                assert (boxes[q, :3] >= lo[i]).all() and (boxes[q, 3:] <= hi[i]).all(), \
+                    f"octant {oct}: a quad of leaf {i} lies outside its box"
+                unb = pads[q] == HUGE
+                assert unb.all() or not unb.any(), f"octant {oct}: leaf {i} mixes bounded and unbounded quads"
+            else:
+                assert end > i + 2, f"octant {oct}: inner node {i} has fewer than two nodes below it"
+                stack.append((end, lo[i], hi[i]))
+        while stack and stack[-1][0] == n:
+            stack.pop()
+        assert not stack
+        assert (seen == 1).all(), "every stored quad is in exactly one leaf"
+        words = np.sort(w[leaf])
+        if leaves is None:
+            leaves, n0 = words, n
+        assert n == n0 and np.array_equal(words, leaves), "the 8 copies hold the same nodes"
+    return r
+
+
+def _leaf_size(device):
+    device._L.rtp_mesh_leaf_size.restype = ctypes.c_int32
+    return int(device._L.rtp_mesh_leaf_size())
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(U)
+
+
+# 1 --------------------------------------------- per-quad records, guarantee --
+@pytest.mark.parametrize("name", ("cornell0", "tess", "facets", "bent", 65536))
+def test_pads_boxes_and_guarantee_equal_the_host(device, name):
+    m = _mesh(name)
+    want = _host(name)
+    g_dev = _set_dev(device, m)
+    got = _readback(device, len(m.quads))
+    g_host = _set_host(device, m)
+    assert _bits(F(g_dev)).tolist() == _bits(F(g_host)).tolist() == _bits(F((want["cos_min"], want["reach"]))).tolist()
+    bad = np.flatnonzero(_bits(got["pads"]) != _bits(want["pads"]))
+    assert bad.size == 0, f"{name}: {bad.size} pads differ, first {bad[:4].tolist()}: {got['pads'][bad[:4]]} " \
+                          f"against {want['pads'][bad[:4]]}"
+    bad = np.flatnonzero((_bits(got["boxes"]) != _bits(want["boxes"])).any(1))
+    assert bad.size == 0, f"{name}: {bad.size} boxes differ, first {bad[:4].tolist()}"
+    huge = np.flatnonzero(got["pads"] == HUGE)
+    assert np.array_equal(huge, np.flatnonzero(want["pads"] == HUGE))
+    if name == "cornell0":
+        assert huge.size == 1
+    if name == "bent":
+        # its 64 strongly bent quads, and of the zoo's own quads the two the host build leaves unbounded as well
+        # (66 in all, by rtp_mesh_build_host); none of the N_MILD mildly bent ones at the end
+        nq = len(m.quads)
+        strongly = np.arange(nq - _meshes.N_MILD - 64, nq - _meshes.N_MILD)
+        assert np.isin(strongly, huge).all() and not (huge >= nq - _meshes.N_MILD).any()
+        assert huge.size == 64 + int((huge < strongly[0]).sum())
+
+
+# 2 ------------------------------------------------------- tree structure --
+def _same_arrays(a, b):
+    return all(np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)) for k in ("cnodes", "order", "boxes", "pads"))
+
+
+@pytest.mark.parametrize("name", ("tess", "bent", "cornell0"))
+def test_tree_structure(device, name):
+    m = _mesh(name)
+    _set_dev(device, m)
+    _check_structure(device, m, _leaf_size(device))
+    first = [_readback(device, len(m.quads), oct) for oct in range(8)]
+    _set_dev(device, m)
+    again = [_readback(device, len(m.quads), oct) for oct in range(8)]
+    assert all(_same_arrays(a, b) for a, b in zip(first, again)), "two builds of one mesh differ"
+
+
+# 3, 4 -------------------------------------------- scan == scan, walk == scan --
+def _scan_winner(out):
+    return np.where(out[:, 4].view(np.int32) == 0, out[:, 5].view(np.int32), -1)
+
+
+def _walk_equals_scan(device, name, n, host_scan=True):
+    m = _mesh(name)
+    cos_min, reach = _set_host(device, m)
+    ray = _meshes.rays(name, cos_min, _pad(name), n)
+    want = device.debug_closest_hit(ray) if host_scan else None
+    assert _set_dev(device, m) == (cos_min, reach)
+    out = device.debug_closest_hit(ray)
+    assert (out[:, 6] == 3).all()
+    if host_scan:
+        bad = np.flatnonzero((out[:, 3:6] != want[:, 3:6]).any(1))
+        assert bad.size == 0, (f"{name}: the scan of the device-built records differs from the host-built ones' on "
+                               f"{bad.size} rays, first {bad[:4].tolist()}: {out[bad[:2], 3:6].tolist()} against "
+                               f"{want[bad[:2], 3:6].tolist()}")
+    inside = _meshes.inside_promise(m, ray, _scan_winner(out), cos_min, reach)
+    part = n // _meshes.N_PARTS
+    for p in range(_meshes.N_PARTS):
+        s = slice(p * part, (p + 1) * part)
+        outside = float((~inside[s]).mean())
+        print(f"{name} {_meshes.PART_NAMES[p]}: {outside:.4f} outside the promise, "
+              f"{int((out[s, :3] != out[s, 3:6]).any(1).sum())} rays differ in all")
+        if p != _meshes.GRAZING:
+            assert outside <= MAX_OUTSIDE, (name, _meshes.PART_NAMES[p], outside)
+    bad = np.flatnonzero(inside & (out[:, :3] != out[:, 3:6]).any(1))
+    assert bad.size == 0, (f"{name}: {bad.size} rays inside the promise: walk != scan; first {bad[:4].tolist()}: "
+                           f"rays {ray[bad[:2]].tolist()} walk {out[bad[:2], :3].tolist()} scan {out[bad[:2], 3:6].tolist()}")
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_scan_equals_scan_and_walk_equals_scan(device, name):
+    _walk_equals_scan(device, name, _meshes.N_RAYS)
+
+
+def test_walk_equals_scan_on_65536_quads(device):
+    _walk_equals_scan(device, 65536, 1 << 14, host_scan=False)
+
+
+# 5 ------------------------------------------------------------------ pixels --
+@pytest.mark.parametrize("cam", CAMS)
+@pytest.mark.parametrize("name", SCENES)
+def test_pixels_equal_the_host_build_and_the_oracle(device, oracle, rtp, name, cam):
+    m = _mesh(name)
+    c = CAMS[cam] or m.cam
+    camera = m.camera(rtp, c)
+    pix = np.arange(NX * NY, dtype=np.int64)
+    _set_host(device, m)
+    host = device.render_pixels(camera, NX, NY, SPP, DEPTH, pix)[:3]
+    _set_dev(device, m)
+    got = device.render_pixels(camera, NX, NY, SPP, DEPTH, pix)[:3]
+    assert_render_equal(got, host, f"{name} {cam}: device build against host build")
+    want = oracle.render_pixels(m.scene(oracle), oracle.camera_setup(NX, NY, **c), NX, NY, SPP, DEPTH, pix)
+    assert_render_equal(got, want, f"{name} {cam}: device build against the oracle")
+
+
+def _golden_pixels(device, rtp, fixture="c1_full", k=None):
+    g = np.load(os.path.join(GOLD, fixture + ".npz"), allow_pickle=False)
+    sel = slice(0, k)
+    n = len(g["pixels"][sel])
+    got = device.render_pixels(rtp.default_camera(), int(g["nx"]), int(g["ny"]), int(g["spp"]), int(g["depth"]),
+                               g["pixels"][sel], seed_base=int(g["seed_base"]))[:3]
+    want = (np.c_[g["rgb"][sel], np.zeros(n, F)], g["final_seed"][sel], g["live"][sel])
+    assert_render_equal(got, want, fixture + " through rtp_set_scene_mesh_device")
+
+
+@pytest.mark.parametrize("variant,fixture", [(0, "c1_full"), (2, "glass2_subset")])
+def test_goldens_through_the_device_build(device, rtp, variant, fixture):
+    _set_dev(device, _meshes.cornell(variant))
+    _golden_pixels(device, rtp, fixture)
+
+
+def test_resume_and_refine(device, rtp):
+    m = _mesh("facets")
+    _set_dev(device, m)
+    cam = m.camera(rtp)
+    nx, ny, depth = 48, 40, 8
+    r = rtp.ProgressiveRender(device, cam, nx, ny, depth)
+    r.step(2)
+    r.step(2)
+    s = r.state()
+    pix = np.arange(nx * ny, dtype=np.int64)
+    assert_render_equal((s["sums"], s["seed"], s["live"]), device.render_pixels(cam, nx, ny, 4, depth, pix)[:3],
+                        "two passes of 2 against one of 4")
+    threshold = float(np.median(noise_ref(s["sums"], s["m2"], s["count"])))
+    ids = np.flatnonzero(active_ref(s["sums"], s["m2"], s["count"], 2, threshold, 16)).astype(np.int64)
+    assert 0.05 < ids.size / (nx * ny) < 0.95
+    assert r.refine_device(2, threshold, 16) == ids.size
+    t = r.state()
+    assert np.array_equal(t["count"][ids], s["count"][ids] + 2)
+    rest = np.setdiff1d(pix, ids)
+    assert np.array_equal(t["sums"][rest].view(U), s["sums"][rest].view(U)) and np.array_equal(t["seed"][rest], s["seed"][rest])
+    assert_render_equal((t["sums"][ids], t["seed"][ids], t["live"][ids]),
+                        device.render_pixels(cam, nx, ny, 6, depth, ids)[:3], "the refined pixels against 6 spp")
+
+
+# 6 ------------------------------------------------------- smallest shapes --
+def _sub(m, quads, extra_points=None, mats=None, texs=None):
+    """`quads` (indices into m's, or point-id rows with mats/texs) in m's room: its points, lights and spheres."""
+    pts = m.points if extra_points is None else np.concatenate([m.points, np.asarray(extra_points, dtype=F)])
+    if mats is None:
+        quads = np.asarray(quads)
+        rows, mats, texs = m.quads[quads], m.quad_mat[quads], m.quad_tex[quads]
+    else:
+        rows = quads
+    return _meshes.Mesh(pts, rows, mats, texs, m.spheres, m.mat_type, m.tex_type, m.tex, m.light, m.light_sphere_point,
+                        m.ior, m.cam)
+
+
+def _edge_meshes(leaf_size):
+    c = _meshes.cornell(0)
+    hp = _host("cornell0")["pads"]
+    bounded, unbounded = np.flatnonzero(hp < HUGE), np.flatnonzero(hp == HUGE)
+    out = {f"n{k}": _sub(c, bounded[:k]) for k in (1, 2, 3, leaf_size + 1)}
+    out["copies64"] = _sub(c, np.full(64, bounded[0]))
+    b = _meshes.bent()
+    nb = len(b.quads) - _meshes.N_MILD
+    out["only_unbounded"] = _sub(b, np.arange(nb - 64, nb))  # bent's 64 strongly bent quads
+    out["one_unbounded"] = _sub(c, np.concatenate([bounded[:3], unbounded[:1]]))
+    # the floor split 4 x 4: every centre has the same y
+    floor = next(q for q in bounded if np.ptp(c.verts()[q][:, 1]) == 0)
+    subs = np.concatenate([s.astype(F) for s in _meshes._split(c.verts()[floor].astype(np.float64), 4)])
+    ids = len(c.points) + np.arange(64).reshape(16, 4)
+    out["one_plane"] = _sub(c, ids, subs, np.full(16, c.quad_mat[floor]), np.full(16, c.quad_tex[floor]))
+    return out
+
+
+EDGES = ("n1", "n2", "n3", "nleaf1", "copies64", "only_unbounded", "one_unbounded", "one_plane")
+
+
+@pytest.mark.parametrize("shape", EDGES)
+def test_smallest_shapes(device, rtp, shape):
+    leaf = _leaf_size(device)
+    meshes = _edge_meshes(leaf)
+    m = meshes[f"n{leaf + 1}" if shape == "nleaf1" else shape]
+    cam = m.camera(rtp)
+    pix = np.arange(16 * 16, dtype=np.int64)
+    _set_host(device, m)
+    want = device.render_pixels(cam, 16, 16, 2, 4, pix)[:3]
+    hb = _meshes.build_host(m)
+    _set_dev(device, m)
+    got = device.render_pixels(cam, 16, 16, 2, 4, pix)[:3]
+    assert_render_equal(got, want, f"{shape}: device build against host build")
+    r = _check_structure(device, m, leaf)
+    assert np.array_equal(_bits(r["pads"]), _bits(hb["pads"])) and np.array_equal(_bits(r["boxes"]), _bits(hb["boxes"]))
+    if shape == "n1":
+        assert len(r["cnodes"]) == 1 and r["cnodes"][0, 3] == (LEAF_BIT | 1)
+    if shape == "only_unbounded":
+        assert (r["pads"] == HUGE).all() and len(m.quads) == 64
+    if shape == "one_unbounded":
+        assert int((r["pads"] == HUGE).sum()) == 1
+    if shape == "one_plane":
+        assert np.ptp(m.verts()[:, :, 1]) == 0 and len(m.quads) == 16
+    if shape == "copies64":
+        # equal keys, split by position: the first copy wins every hit, in the walk as in the scan
+        lo, hi = m.bounds()
+        rng = np.random.default_rng(5)
+        o = lo + (hi - lo) * rng.uniform(0.1, 0.9, size=(4096, 3))
+        tgt = m.verts()[0].astype(np.float64)
+        ab = rng.uniform(0.05, 0.95, size=(4096, 2))
+        p = tgt[0] + ab[:, :1] * (tgt[1] - tgt[0]) + ab[:, 1:] * (tgt[3] - tgt[0])
+        ray = np.concatenate([o, p - o], 1).astype(F)
+        out = device.debug_closest_hit(ray)
+        hit = out[:, 1].view(np.int32) == 0
+        inside = _meshes.inside_promise(m, ray, _scan_winner(out), *device.mesh_guarantee())
+        assert hit.sum() > 1024 and inside.mean() > 0.99 and np.array_equal(out[inside, :3], out[inside, 3:6])
+        assert (out[hit, 2] == 0).all(), "a later copy of the quad won a hit"
+
+
+# 7 -------------------------------------------------------------- refusals --
+def _message(call):
+    from raytracingtherestofyourlife_amd import _lib
+
+    with pytest.raises(_lib.RtpError) as e:
+        call()
+    assert e.value.status == _lib.RTP_ERR_INVALID_ARGUMENT
+    return str(e.value)
+
+
+def test_refusals(device, rtp):
+    import torch
+
+    from raytracingtherestofyourlife_amd import _lib
+    from raytracingtherestofyourlife_amd.device import scene_desc
+
+    m = _mesh("tess")
+    nq = len(m.quads)
+    _set_dev(device, _meshes.cornell(0))
+    _golden_pixels(device, rtp, k=256)
+
+    def faulty(what):
+        pts, quads, mat = m.points.copy(), m.quads.copy(), m.quad_mat.copy()
+        sph = m.spheres
+        if what == "point":
+            quads[nq - 1, 2] = len(pts)
+        elif what == "nan":
+            pts[quads[0, 1], 2] = np.nan
+        elif what == "material":
+            mat[nq // 2] = len(m.mat_type)
+        elif what == "spheres":
+            sph = [m.spheres[0]] * 9
+        return _meshes.Mesh(pts, quads, mat, m.quad_tex, sph, m.mat_type, m.tex_type, m.tex, m.light,
+                            m.light_sphere_point, m.ior)
+
+    words = {"point": "quad point id out of range", "nan": "a quad vertex is not finite",
+             "material": "quad material/texture index out of range", "spheres": "at most 8 spheres"}
+    for what, word in words.items():
+        bad = faulty(what)
+        host = _message(lambda: device.set_scene_mesh(*bad.set_args()))
+        _set_dev(device, _meshes.cornell(0))  # (the host refusal left the Cornell box; make it the device-built one)
+        dev = _message(lambda: _set_dev(device, bad))
+        assert dev == host and word in dev, (what, dev, host)
+        _golden_pixels(device, rtp, k=256)  # the previous scene still renders
+    # NULL device pointers
+    d, keep = scene_desc(*m.set_args())
+    for field in ("points", "quad_points", "quad_mat", "quad_tex"):
+        t = _tensors(m)
+        d.points, d.quad_points = ctypes.cast(t[0].data_ptr(), _lib.f32p), ctypes.cast(t[1].data_ptr(), _lib.i32p)
+        d.quad_mat, d.quad_tex = ctypes.cast(t[2].data_ptr(), _lib.i32p), ctypes.cast(t[3].data_ptr(), _lib.i32p)
+        setattr(d, field, None)
+        assert device._L.rtp_set_scene_mesh_device(device.handle, d, None) == _lib.RTP_ERR_INVALID_ARGUMENT, field
+        _golden_pixels(device, rtp, k=256)
+    assert device._L.rtp_set_scene_mesh_device(device.handle, None, None) == _lib.RTP_ERR_INVALID_ARGUMENT
+    del keep
+    # the binding refuses what is no tensor of the right kind on the GPU before any call
+    t = _tensors(m)
+    rest = m.set_args()[4:]
+    for k, wrong in ((0, t[0].cpu()), (0, t[0].double()), (1, t[1].long()), (2, m.quad_mat), (1, t[1].t()),
+                     (0, t[0][:, :2])):
+        args = list(t)
+        args[k] = wrong
+        with pytest.raises(ValueError):
+            device.set_scene_mesh_device(*args, *rest)
+    torch.cuda.synchronize()
+    _golden_pixels(device, rtp, k=256)
+
+
+# 8 -------------------------------------------------------------- time steps --
+def test_time_steps(device, rtp):
+    import torch
+
+    m = _mesh("tess")
+    cam = rtp.default_camera()
+    pix = np.arange(NX * NY, dtype=np.int64)
+    base = _tensors(m)[0]
+    lo, hi = base.min(0).values, base.max(0).values
+    ctr, size = 0.5 * (lo + hi), float((hi - lo).max())
+    side = torch.cuda.Stream()
+
+    def displaced(k):
+        # a shear that grows with the step: a few percent of the scene's size, planar quads stay planar
+        rel = (base - ctr) / size
+        return (base + (0.02 * (k + 1) * size) * torch.stack([rel[:, 1], rel[:, 2] * 0.5, rel[:, 0] * -0.75], 1)).contiguous()
+
+    coords, streams = [], []
+    for k in range(4):
+        if k == 2:  # produced on a stream of its own, which the build is then queued on
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                coords.append(displaced(k))
+            streams.append(side)
+        else:
+            coords.append(displaced(k))
+            streams.append(None)
+    torch.cuda.current_stream().synchronize()  # (stream `side` is not waited for: the build's stream order does that)
+    hosts = [None] * 4
+    free = []
+    got = []
+    for k in range(4):
+        _set_dev(device, m, coords[k], streams[k])
+        free.append(torch.cuda.mem_get_info()[0])
+        got.append(device.render_pixels(cam, NX, NY, SPP, DEPTH, pix)[:3])
+    assert free[3] >= free[1], f"free device memory fell from {free[1]} after the 2nd build to {free[3]} after the 4th"
+    torch.cuda.synchronize()
+    for k in range(4):
+        hosts[k] = coords[k].cpu().numpy()
+        assert 0.004 * size < np.abs(hosts[k] - m.points).max() < 0.1 * size
+        moved = _meshes.Mesh(hosts[k], m.quads, m.quad_mat, m.quad_tex, m.spheres, m.mat_type, m.tex_type, m.tex, m.light,
+                             m.light_sphere_point, m.ior)
+        _set_host(device, moved)
+        assert_render_equal(got[k], device.render_pixels(cam, NX, NY, SPP, DEPTH, pix)[:3], f"time step {k}")
+    assert not np.array_equal(got[0][0], got[3][0])
+
+
+# 9 ------------------------------------------------------- RTP_MESH_BUILD=gpu --
+def test_env_switch(device, rtp, monkeypatch):
+    m = _mesh("tess")
+    nq = len(m.quads)
+    cam = m.camera(rtp)
+    pix = np.arange(NX * NY, dtype=np.int64)
+    monkeypatch.delenv("RTP_MESH_BUILD", raising=False)
+    _set_host(device, m)
+    want = device.render_pixels(cam, NX, NY, SPP, DEPTH, pix)[:3]
+    assert np.array_equal(_readback(device, nq)["order"], _host("tess")["order"]), "unset: the host build"
+    monkeypatch.setenv("RTP_MESH_BUILD", "host")
+    _set_host(device, m)
+    assert np.array_equal(_readback(device, nq)["order"], _host("tess")["order"]), "host: the host build"
+    _set_dev(device, m)
+    tensor_path = [_readback(device, nq, oct) for oct in (0, 5)]
+    monkeypatch.setenv("RTP_MESH_BUILD", "gpu")
+    _set_host(device, m)
+    assert all(_same_arrays(_readback(device, nq, oct), t) for oct, t in zip((0, 5), tensor_path))
+    assert_render_equal(device.render_pixels(cam, NX, NY, SPP, DEPTH, pix)[:3], want, "RTP_MESH_BUILD=gpu")

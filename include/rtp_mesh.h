@@ -29,11 +29,33 @@ extern "C" {
  * cos_min = 2^-8, theta the angle to the plane's normal.  Outside it (origins
  * far away, rays within 0.22 degrees of the plane) the float32 test accepts
  * points arbitrarily far from the quad, and the walk may miss what the scan
- * would report.  A quad whose fourth vertex is off the first triangle's plane
- * by 1/512 or more of its distance beyond the diagonal gets an unbounded box:
- * always tested, sound, slow -- a mesh made mostly of such quads renders as
- * slowly as a brute-force scan.  rtp_mesh_guarantee returns cos_min and reach of
- * the current mesh scene.  (csrc/rtp_layout.hpp kMeshCosMin.)
+ * would report.  rtp_mesh_guarantee returns cos_min and reach of the current
+ * mesh scene.  (csrc/rtp_layout.hpp kMeshCosMin.)
+ *
+ * Bent quads and triangle cells.  A quad whose third vertex v11 is off the
+ * first triangle's plane by 1/512 or more of its distance beyond the diagonal
+ * gets an unbounded box, because the reference's test accepts such a quad
+ * arbitrarily far away: always tested, sound, slow -- a mesh made mostly of
+ * such quads renders as slowly as a brute-force scan, and a curved surface
+ * given as quads is such a mesh.  Give it as triangles.  A triangle cell is a
+ * cell whose v11 and v01 compare equal in all three coordinates, in
+ * particular (a, b, c, c): the same point named as third and fourth id, the
+ * usual way to state a triangle in a quad list.  Its meaning is what the
+ * reference makes of that quad -- exactly its first triangle (v00, v10, v01)
+ * with the normal of (v00, v10, v11 = v01), same closest hit, tie-break and
+ * pixels -- and it always gets a tight box: its three vertices and a pad that
+ * depends on the corner at v00 alone (unbounded only for a corner whose sine
+ * is below 2^-10 or a pad beyond the reach).  A triangle costs one box, one
+ * record and one test, like a planar quad (a 16 384-cell curved terrain as
+ * 32 768 triangles: 12 ms a frame where its bent quads take 3.5 s, DESIGN.md
+ * 4.11).  So split the bent quads of a mesh: (v00, v10, v11, v01) becomes (v00, v10,
+ * v01, v01) and (v11, v01, v10, v10), both with the quad's orientation.  The
+ * two halves are not the reference's bent quad: each reports t on its own
+ * plane and accepts nothing beyond its edges -- which is the point.
+ * rtp_mesh_counts reports the cells, the triangle cells among them and the
+ * cells with an unbounded box of the current mesh scene (each output
+ * optional): n_unbounded says why a mesh is slow.  It fails with
+ * RTP_ERR_INVALID_ARGUMENT when the context holds no mesh scene.
  *
  * On a mesh scene rtp_render, rtp_render_device (range and pixel list; work
  * stealing), rtp_render_pixels, rtp_render_resume*, rtp_render_views* (the
@@ -45,6 +67,7 @@ extern "C" {
  * of the scene scan all its quads instead of walking: the A/B handle. */
 rtp_status rtp_set_scene_mesh(rtp_context* ctx, const rtp_scene_desc* scene);
 rtp_status rtp_mesh_guarantee(rtp_context* ctx, float* cos_min, float* reach);
+rtp_status rtp_mesh_counts(rtp_context* ctx, int32_t* n_cells, int32_t* n_triangles, int32_t* n_unbounded);
 
 /* The same scene from arrays that already live on the context's device, for
  * cell sets a simulation moves every time step: `points`, `quad_points`,

@@ -3,6 +3,7 @@ m-kim/raytracingtherestofyourlife (MapperPathTracer::RenderCellsImpl) as HIP
 kernels for gfx950 behind a C ABI (include/rtp.h, librtp.so)."""
 from ._lib import LIB_PATH, RtpError, load  # noqa: F401
 from .device import Device  # noqa: F401
+from .mesh import mesh_pads, triangulate, unbounded_cells  # noqa: F401
 from .mapper import (  # noqa: F401
     Camera, CanvasRayTracer, CellSet, CornellBox, DataSet, ErrorBadValue, MapperPathTracer,
     Field, default_camera, hemisphere_cameras, normalize, runPath, runPathProgressive, runPathViews, save_pnm,
@@ -21,5 +22,5 @@ __all__ = [
     "Field", "Actor", "Color", "ColorTable", "MapperQuad", "MapperQuadAlbedo", "MapperQuadNormals", "Scene",
     "View3D", "runAlbedo", "runDirect", "runNorms", "runRay", "save_depth_pnm", "hemisphere_cameras", "runPathViews",
     "runPathProgressive", "ProgressiveRender", "noise_from_state", "select_active", "split_passes",
-    "adaptive", "normalize_counts",
+    "adaptive", "normalize_counts", "mesh_pads", "triangulate", "unbounded_cells",
 ]

@@ -156,6 +156,11 @@ MESH_SIGNATURES = {
     "rtp_mesh_guarantee": (ctypes.c_int32, [vp, f32p, f32p]),
     "rtp_set_scene_mesh_device": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc), vp]),
 }
+# include/rtp_mesh.h, triangle cells: the later additions in a table of their
+# own (MESH_SIGNATURES is the mesh scenes' first three), bound by load() too
+MESH_TRI_SIGNATURES = {
+    "rtp_mesh_counts": (ctypes.c_int32, [vp, i32p, i32p, i32p]),
+}
 
 
 class RtpError(RuntimeError):
@@ -195,7 +200,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     # baselines of the tools/*_bench.py): it loads without them, and calling
     # one raises AttributeError.  The in-tree library must export them all.
     missing = []
-    for name, (restype, argtypes) in {**SIGNATURES, **MESH_SIGNATURES}.items():
+    for name, (restype, argtypes) in {**SIGNATURES, **MESH_SIGNATURES, **MESH_TRI_SIGNATURES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:

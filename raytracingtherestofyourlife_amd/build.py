@@ -130,6 +130,7 @@ ASAN_PROGRAMS = {
     os.path.join(ASAN_DIR, "shim_check"): os.path.join(ROOT, "tests", "cpp", "shim_check.cpp"),
     os.path.join(ASAN_DIR, "asan_adaptive"): os.path.join(ROOT, "tests", "cpp", "asan_adaptive.cpp"),
     os.path.join(ASAN_DIR, "asan_mesh"): os.path.join(ROOT, "tests", "cpp", "asan_mesh.cpp"),
+    os.path.join(ASAN_DIR, "asan_mesh_tri"): os.path.join(ROOT, "tests", "cpp", "asan_mesh_tri.cpp"),
 }
 # AddressSanitizer + UBSan on host code only (GPU sanitizers are not available
 # on the pool): each -fsanitize= directly after -Xarch_host.  The sanitizer

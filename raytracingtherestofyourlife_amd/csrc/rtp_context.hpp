@@ -44,6 +44,8 @@ struct rtp_context {
   // (6 floats) and pad in the caller's order -- on the device after the device
   // build (rtp_set_scene_mesh_device), on the host after the host build
   int32_t n_mesh_nodes = 0, n_mesh_quads = 0;
+  // rtp_mesh_counts: the triangle cells, and the cells with the unbounded box
+  int32_t n_mesh_triangles = 0, n_mesh_unbounded = 0;
   float* d_mesh_boxes = nullptr;
   float* d_mesh_pads = nullptr;
   std::vector<float> h_mesh_boxes, h_mesh_pads;

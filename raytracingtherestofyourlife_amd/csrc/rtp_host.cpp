@@ -948,6 +948,8 @@ rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) 
   c->mesh_reach = B.mesh ? B.mb.reach : 0.f;
   c->n_mesh_nodes = B.mesh ? h->n_mesh_nodes : 0;
   c->n_mesh_quads = B.mesh ? h->n_mesh_quads : 0;
+  c->n_mesh_triangles = B.mesh ? B.mb.n_triangles : 0;
+  c->n_mesh_unbounded = B.mesh ? B.mb.n_unbounded : 0;
   c->lw_bytes = h->n_lw_nodes > 0 ? 16 * (8 * h->n_lw_nodes + h->n_lw_sph) : 0;
   c->use_bvh = B.use_bvh;
   c->oct_mask = B.use_bvh ? h->oct_mask : 0;
@@ -1033,6 +1035,8 @@ rtp_status set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, hipStr
   UPLOAD_TRY(rtp_mesh_gpu_build(&in, B.mb.reach, &B.mesh_dev, &open_tree, stream));
   if (open_tree) return fail(RTP_ERR_DEVICE, "rtp_set_scene_mesh_device: the radix tree did not close");
   B.mesh_on_device = true;
+  B.mb.n_triangles = B.mesh_dev.n_triangles;
+  B.mb.n_unbounded = B.mesh_dev.n_unbounded;
   h->n_mesh_nodes = B.mesh_dev.n_nodes;
   h->n_mesh_quads = s->n_quads;
   h->mesh_scan = env_is("RTP_MESH_SCAN", '1') ? 1 : 0;
@@ -1103,6 +1107,8 @@ rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
     rtp::DevQuad& Q = B.mesh_quads[j];
     fill_quad(Q, ld(s->points + 3 * id[0]), ld(s->points + 3 * id[1]), ld(s->points + 3 * id[2]),
               ld(s->points + 3 * id[3]));
+    // a triangle cell's mark, in the mesh record only (rtp_trace.hpp mesh_quad_test)
+    if (rtp::mesh_is_triangle(s->points + 3 * id[2], s->points + 3 * id[3])) Q.kind = rtp::kMeshKindTri;
     Q.mt = s->mat_type[s->quad_mat[q]];
     st(Q.alb, ld(s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]]));
     Q.orig = q;
@@ -1154,11 +1160,31 @@ rtp_status rtp_debug_mesh_readback(rtp_context* c, int32_t oct, int32_t node_cap
   return RTP_OK;
 }
 
+// test hook (rtp_mesh.hpp): the stored records of the current mesh scene, whole, in leaf order
+rtp_status rtp_debug_mesh_records(rtp_context* c, int64_t cap, void* records) {
+  if (!c || !c->has_scene || !c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_records: the context holds no mesh scene");
+  if (!records || cap < c->n_mesh_quads) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_records: cap too small");
+  HIP_TRY(hipSetDevice(c->device));
+  RTP_TRY(drain(c));
+  HIP_TRY(hipMemcpy(records, c->d_mesh_quads, sizeof(rtp::DevQuad) * (size_t)c->n_mesh_quads, hipMemcpyDeviceToHost));
+  return RTP_OK;
+}
+
 rtp_status rtp_mesh_guarantee(rtp_context* c, float* cos_min, float* reach) {
   if (!c || !c->has_scene || !c->is_mesh)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_mesh_guarantee: the context holds no mesh scene");
   if (cos_min) *cos_min = rtp::kMeshCosMin;
   if (reach) *reach = c->mesh_reach;
+  return RTP_OK;
+}
+
+rtp_status rtp_mesh_counts(rtp_context* c, int32_t* n_cells, int32_t* n_triangles, int32_t* n_unbounded) {
+  if (!c || !c->has_scene || !c->is_mesh)
+    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_mesh_counts: the context holds no mesh scene");
+  if (n_cells) *n_cells = c->n_mesh_quads;
+  if (n_triangles) *n_triangles = c->n_mesh_triangles;
+  if (n_unbounded) *n_unbounded = c->n_mesh_unbounded;
   return RTP_OK;
 }
 

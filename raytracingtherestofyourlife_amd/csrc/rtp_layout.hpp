@@ -209,10 +209,56 @@ inline float bvh_sphere_pad(float cx, float cy, float cz, float r, float reach) 
 // = 2^-8: on the Cornell box (diagonal 1.73, s = 1) the pad is 2^-18 * 3.46 *
 // 256 = 3.4e-3, 0.2% of the diagonal on each side of every box -- the cull
 // it costs; rays within 0.22 degrees of a quad's plane are outside the promise.
+//
+// Triangle cells.  A cell whose v11 and v01 compare equal in all three
+// coordinates -- (a, b, c, c), the usual way to state a triangle as a quad --
+// has e23 = v01 - v11 = +-0 in every component.  Where alpha + beta > 1 the
+// test computes detp = e23 . Pp, a sum of three zero products (Pp is finite
+// for finite rays), so |detp| < 1e-5 and the branch rejects: under the
+// reference's own code the cell is its first triangle (v00, v10, v01) and
+// nothing else.  For the pad:
+//   item 1 does not arise.  An accepted hit has alpha, beta >= 0 and
+//     alpha + beta <= 1 as float32 computes them, so there is no second cone,
+//     no h (v11 is v01, on P1) and no fold to test; the accepted region is
+//     the triangle widened by item 2, and its box is that of the three
+//     vertices -- the far corner v00 + e01 + e03 is not in it;
+//   item 2 applies unchanged: it bounds the first-triangle arithmetic alone,
+//     with s the sine of the corner at v00, A1 / (|e01| |e03|) -- the corner
+//     at v11, whose sine the quad's pad also takes, belongs to the second
+//     test.  The rounding of alpha + beta itself (u relative to a sum near 1)
+//     moves the edge (v10, v01) by less than u of an edge, inside the 3.5 u
+//     reach / (s cos) that kMeshRound leaves over the 60.5 derived above;
+//   item 3 applies unchanged.
+// So pad = (kMeshRound reach / s) / kMeshCosMin + slab, and the box is
+// unbounded only for A1 not positive and finite, s < kMeshMinSine, or pad >=
+// reach.  The walk may then reject a marked cell on alpha + beta > 1 without
+// reading e21 / e23 (rtp_trace.hpp mesh_quad_test, RTP_MESH_TRI_TEST).
 constexpr float kMeshCosMin = 0x1p-8f;
 constexpr float kMeshRound = 0x1p-18f;    // 64 * 2^-24
 constexpr float kMeshMinSine = 0x1p-10f;  // flatter corners: the unbounded box
 constexpr float kMeshHuge = 0x1p100f;     // the unbounded box's half extent (rounds to +-inf in half precision)
+// DevQuad::kind of a triangle cell's mesh record (the walk runs the general
+// test whatever the kind; the inline scene's records never carry it)
+constexpr int32_t kMeshKindTri = -1;
+// The walk's test of a marked triangle cell: 1 rejects on alpha + beta > 1
+// without the record's e21 / e23 tail, 0 runs the general test (the same
+// result: the second triangle's branch can only reject).  Default 0: with
+// the branch the four mesh pool instances keep 95 VGPRs and 12 B of scratch
+// and triangle terrains render 2% to 8% faster, but planar quad meshes came
+// out 1% to 3% slower than the parent commit, outside the spread of two
+// copies of the parent (DESIGN.md 4.11 "Triangle cells",
+// profiles/mesh_tri_bench.txt).  With 0 the walk's kernels are the
+// parent's, instruction for instruction; the triangle cells' gain is their
+// boxes.  tools/build_variant.sh out.so -DRTP_MESH_TRI_TEST=1 builds the other.
+#ifndef RTP_MESH_TRI_TEST
+#define RTP_MESH_TRI_TEST 0
+#endif
+#ifdef __HIP__
+__attribute__((host)) __attribute__((device))
+#endif
+inline bool mesh_is_triangle(const float* v11, const float* v01) {
+  return v11[0] == v01[0] && v11[1] == v01[1] && v11[2] == v01[2];
+}
 
 // leaf value of a one-sphere leaf that holds the sphere itself: lo = centre,
 // hi[0] = radius^2, hi[1] = sphere index (int bits)

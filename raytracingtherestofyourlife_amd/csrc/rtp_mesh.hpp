@@ -16,6 +16,8 @@ struct MeshBuild {
   std::vector<float> boxes;         // 6 per quad, the caller's order: the padded box (lo, hi)
   std::vector<float> pads;          // per quad: the pad (kMeshHuge: the unbounded box)
   float reach = 0.f;                // the promise's reach (kBvhReachFactor scene diagonals)
+  int32_t n_triangles = 0;          // rtp_mesh_counts: the triangle cells (v11 == v01) ...
+  int32_t n_unbounded = 0;          // ... and the cells with the unbounded box
 };
 
 // the descriptor checks of rtp_set_scene_mesh (rtp_set_scene's, and the mesh scene's counts)
@@ -57,4 +59,10 @@ extern "C" rtp_status rtp_mesh_scan_host(const rtp_scene_desc* scene, const floa
 // optional.
 extern "C" rtp_status rtp_debug_mesh_readback(rtp_context* ctx, int32_t oct, int32_t node_cap, int32_t* n_nodes,
                                               void* cnodes, int32_t* order, float* boxes, float* pads);
+// Likewise: the stored records themselves (rtp::DevQuad, 128 bytes each, at
+// most cap of them) in leaf order -- a triangle cell's carries kMeshKindTri in
+// its kind word whichever builder wrote it.  A hook of its own: a `records`
+// argument on rtp_debug_mesh_readback would change the signature that
+// existing callers of that hook bind.
+extern "C" rtp_status rtp_debug_mesh_records(rtp_context* ctx, int64_t cap, void* records);
 

@@ -4,8 +4,9 @@
 //
 //   1. k_validate   mesh_validate's per-quad checks (the first failure by
 //                   lowest quad index) and the min / max of the vertices;
-//   2. k_boxes      each quad's pad (double, quad_pad's operations), padded
-//                   box and box centre; the centres' bounds;
+//   2. k_boxes      each quad's pad (double, quad_pad's operations; tri_pad's
+//                   for a triangle cell, v11 == v01), padded box and box
+//                   centre; the centres' bounds; the counts of rtp_mesh_counts;
 //   3. k_morton     30-bit Morton code of the centre, bit 30 for a quad with
 //                   the unbounded box: those sort behind all others and the
 //                   radix tree splits them off near its root;
@@ -122,6 +123,19 @@ __device__ float quad_pad(d3 q, d3 r, d3 s, d3 t, double reach, double amax) {
   if (!(pad < reach)) return kMeshHuge;
   return next_up((float)pad);
 }
+// rtp_mesh_host.cpp tri_pad, operation for operation
+__device__ float tri_pad(d3 q, d3 r, d3 t, double reach, double amax) {
+  const d3 e01 = subd(r, q), e03 = subd(t, q);
+  const double A1 = lend(crossd(e01, e03));
+  const double l1 = lend(e01) * lend(e03);
+  if (!(A1 > 0) || !finite_d(A1)) return kMeshHuge;
+  const double sine = A1 / l1;
+  if (!(sine >= kMeshMinSine)) return kMeshHuge;
+  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
+  const double pad = ((double)kMeshRound * reach / sine) / (double)kMeshCosMin + slab;
+  if (!(pad < reach)) return kMeshHuge;
+  return next_up((float)pad);
+}
 
 // a block's min / max of three floats per thread into six global keys
 struct BlockBounds {
@@ -180,22 +194,33 @@ __global__ void k_validate(MeshGpuIn in, MeshGpuInfo* __restrict__ info) {
 __global__ void k_boxes(MeshGpuIn in, float reach, float* __restrict__ boxes, float* __restrict__ pads,
                         float* __restrict__ cen, MeshGpuInfo* __restrict__ info) {
   __shared__ BlockBounds sb;
+  __shared__ uint32_t counts[2];  // this block's triangle cells and unbounded boxes (rtp_mesh_counts)
+  if (threadIdx.x < 2) counts[threadIdx.x] = 0u;
   bounds_init(sb);
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q < in.n_quads) {
     f3 v[4];
     for (int k = 0; k < 4; k++) v[k] = load_point(in.points, in.quad_points[4 * (int64_t)q + k]);
+    const bool tri = mesh_is_triangle(&v[2].x, &v[3].x);
     float mn[3], mx[3];
     for (int k = 0; k < 3; k++) {
       const float a = (&v[0].x)[k], b = (&v[1].x)[k], c = (&v[2].x)[k], d = (&v[3].x)[k];
+      if (tri) {  // a triangle cell: its three vertices
+        mn[k] = hmin(hmin(a, b), d);
+        mx[k] = hmax(hmax(a, b), d);
+        continue;
+      }
       const float far = a + (b - a) + (d - a);  // v00 + e01 + e03 with the records' float edges
       mn[k] = hmin(hmin(hmin(a, b), hmin(c, d)), far);
       mx[k] = hmax(hmax(hmax(a, b), hmax(c, d)), far);
     }
     double amax = 0;
     for (int k = 0; k < 3; k++) amax = hmaxd(amax, (double)hmax(fabsf(mn[k]), fabsf(mx[k])));
-    const float pad = quad_pad(todouble(v[0]), todouble(v[1]), todouble(v[2]), todouble(v[3]), reach, amax);
+    const float pad = tri ? tri_pad(todouble(v[0]), todouble(v[1]), todouble(v[3]), reach, amax)
+                          : quad_pad(todouble(v[0]), todouble(v[1]), todouble(v[2]), todouble(v[3]), reach, amax);
     pads[q] = pad;
+    if (tri) atomicAdd(&counts[0], 1u);
+    if (pad == kMeshHuge) atomicAdd(&counts[1], 1u);
     f3 c;
     for (int k = 0; k < 3; k++) {
       boxes[6 * (int64_t)q + k] = next_down(mn[k] - pad);
@@ -205,7 +230,9 @@ __global__ void k_boxes(MeshGpuIn in, float reach, float* __restrict__ boxes, fl
     }
     bounds_add(sb, c);
   }
-  bounds_flush(sb, info->clo, info->chi);
+  bounds_flush(sb, info->clo, info->chi);  // (its barrier also closes this block's counts)
+  if (threadIdx.x == 0 && counts[0]) atomicAdd(&info->n_triangles, counts[0]);
+  if (threadIdx.x == 1 && counts[1]) atomicAdd(&info->n_unbounded, counts[1]);
 }
 
 // -------------------------------------------------------------- 3 morton ---
@@ -428,6 +455,7 @@ __global__ void k_quads(MeshGpuIn in, const uint32_t* __restrict__ idx, float4* 
   for (int k = 1; k < kQuadKinds; k++)
     if (kQuadKind[k].m01 == m01 && kQuadKind[k].m03 == m03 && kQuadKind[k].m21 == m21 && kQuadKind[k].m23 == m23)
       kind = k;
+  if (mesh_is_triangle(&s.x, &t.x)) kind = kMeshKindTri;  // a triangle cell's mark (rtp_set_scene_mesh's record)
   const int32_t mt = in.mat_chk[in.quad_mat[qi]];
   const float* rgb = in.tex_rgb + 3 * in.tex_chk[in.quad_tex[qi]];
   const float a0 = rgb[0], a1 = rgb[1], a2 = rgb[2];
@@ -563,6 +591,8 @@ extern "C" hipError_t rtp_mesh_gpu_build(const rtp::MeshGpuIn* in, float reach, 
   int root[2] = {kPending, 0};
   MESH_TRY(hipMemcpyAsync(&root[0], level, sizeof(int), hipMemcpyDeviceToHost, stream));
   MESH_TRY(hipMemcpyAsync(&root[1], size, sizeof(int), hipMemcpyDeviceToHost, stream));
+  MeshGpuInfo counted;  // the 64-byte record again, for k_boxes' two counts
+  MESH_TRY(hipMemcpyAsync(&counted, d_info, sizeof(counted), hipMemcpyDeviceToHost, stream));
   MESH_TRY(hipStreamSynchronize(stream));
   if (root[0] < 0 || root[1] < 1 || root[1] > nn) {
     *status = 1;
@@ -570,6 +600,8 @@ extern "C" hipError_t rtp_mesh_gpu_build(const rtp::MeshGpuIn* in, float reach, 
     return hipSuccess;
   }
   out->n_nodes = root[1];
+  out->n_triangles = (int32_t)counted.n_triangles;
+  out->n_unbounded = (int32_t)counted.n_unbounded;
   MESH_TRY(dalloc(&out->nodes, (size_t)8 * 4 * out->n_nodes));
   hipLaunchKernelGGL(k_flatten, dim3(blocks(nn)), dim3(kTb), 0, stream, n, out->n_nodes, child, parent, axis, blo, bhi,
                      size, level, word, reinterpret_cast<uint4*>(out->nodes));

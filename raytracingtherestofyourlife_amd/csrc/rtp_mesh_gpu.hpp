@@ -39,7 +39,9 @@ struct MeshGpuInfo {
   uint32_t first_fail;  // min over the failing quads of (q << 2 | MeshGpuFail); kMeshNoFail: none
   uint32_t lo[3], hi[3];    // min / max over all quad vertices
   uint32_t clo[3], chi[3];  // min / max over the box centres (the Morton codes' frame; device only)
-  uint32_t pad[3];
+  uint32_t n_triangles;     // k_boxes: the triangle cells (v11 == v01) ...
+  uint32_t n_unbounded;     // ... and the cells whose box is unbounded (rtp_mesh_counts)
+  uint32_t pad[1];
 };
 static_assert(sizeof(MeshGpuInfo) == 64, "one small record");
 
@@ -59,6 +61,8 @@ struct MeshGpuOut {
   float* boxes = nullptr;     // 6 floats per quad, caller's order
   float* pads = nullptr;      // 1 float per quad
   int32_t n_nodes = 0;        // per octant copy
+  int32_t n_triangles = 0;    // MeshGpuInfo's counts, read back with the root
+  int32_t n_unbounded = 0;
 };
 
 }  // namespace rtp

@@ -56,6 +56,23 @@ float quad_pad(d3 q, d3 r, d3 s, d3 t, double reach, double amax) {
   return std::nextafter((float)pad, INFINITY);
 }
 
+// The pad of a triangle cell (v11 == v01: the reference's test accepts only
+// its first triangle v00 = q, v10 = r, v01 = t): the roundings and the slab
+// terms of quad_pad over the sine of the corner at v00 alone, no h and no fold
+// (rtp_layout.hpp kMeshCosMin, "Triangle cells").
+float tri_pad(d3 q, d3 r, d3 t, double reach, double amax) {
+  const d3 e01 = r - q, e03 = t - q;
+  const double A1 = len(crossd(e01, e03));
+  const double l1 = len(e01) * len(e03);
+  if (!(A1 > 0) || !std::isfinite(A1)) return rtp::kMeshHuge;
+  const double sine = A1 / l1;
+  if (!(sine >= rtp::kMeshMinSine)) return rtp::kMeshHuge;
+  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
+  const double pad = ((double)rtp::kMeshRound * reach / sine) / (double)rtp::kMeshCosMin + slab;
+  if (!(pad < reach)) return rtp::kMeshHuge;
+  return std::nextafter((float)pad, INFINITY);
+}
+
 // the ordered key of a half: key k >= 0 is the half with bits k, k < 0 its negative
 float half_value(int key) {
   const int b = key < 0 ? -key : key;
@@ -152,12 +169,20 @@ rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
   if (!std::isfinite(B.reach)) return mesh_bounds_fail();
   B.boxes.resize((size_t)6 * n);
   B.pads.resize(n);
+  B.n_triangles = B.n_unbounded = 0;
   std::vector<BvhPrim> P(n);
   for (int q = 0; q < n; q++) {
     const float* v[4];
     for (int c = 0; c < 4; c++) v[c] = s->points + 3 * s->quad_points[4 * q + c];
+    // a triangle cell: v11 and v01 compare equal (include/rtp_mesh.h)
+    const bool tri = rtp::mesh_is_triangle(v[2], v[3]);
     float mn[3], mx[3];
     for (int k = 0; k < 3; k++) {
+      if (tri) {  // the accepted region is the triangle: its three vertices
+        mn[k] = std::min(std::min(v[0][k], v[1][k]), v[3][k]);
+        mx[k] = std::max(std::max(v[0][k], v[1][k]), v[3][k]);
+        continue;
+      }
       // the four vertices and v00 + e01 + e03 with the device's float edges
       const float far = v[0][k] + (v[1][k] - v[0][k]) + (v[3][k] - v[0][k]);
       mn[k] = std::min(std::min(std::min(v[0][k], v[1][k]), std::min(v[2][k], v[3][k])), far);
@@ -165,8 +190,11 @@ rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
     }
     double amax = 0;
     for (int k = 0; k < 3; k++) amax = std::max(amax, (double)std::max(std::fabs(mn[k]), std::fabs(mx[k])));
-    const float pad = quad_pad(ldd(v[0]), ldd(v[1]), ldd(v[2]), ldd(v[3]), B.reach, amax);
+    const float pad = tri ? tri_pad(ldd(v[0]), ldd(v[1]), ldd(v[3]), B.reach, amax)
+                          : quad_pad(ldd(v[0]), ldd(v[1]), ldd(v[2]), ldd(v[3]), B.reach, amax);
     B.pads[q] = pad;
+    B.n_triangles += tri ? 1 : 0;
+    B.n_unbounded += pad == rtp::kMeshHuge ? 1 : 0;
     for (int k = 0; k < 3; k++) {
       // (one step outward: the float sums may round toward the quad)
       P[q].lo[k] = B.boxes[6 * (size_t)q + k] = std::nextafter(mn[k] - pad, -INFINITY);

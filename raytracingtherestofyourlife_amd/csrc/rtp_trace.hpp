@@ -244,6 +244,25 @@ RTP_DEV void spheres_bvh(const DevScene* __restrict__ sc, f3 o, f3 d, Hit& h) {
 // read from memory only by lanes whose quad is no exact parallelogram and
 // whose alpha + beta > 1.  By the zero-structure argument of rtp_device.hpp
 // the general test equals the kind-specific ones on finite rays.
+// A triangle cell (kind == kMeshKindTri: v11 == v01, so e23 == 0) is the
+// first triangle alone: where alpha + beta > 1 the general test's second
+// branch computes detp = e23 . Pp = 0 and rejects (rtp_layout.hpp kMeshCosMin,
+// "Triangle cells").  mesh_tri_hit is the first-triangle arithmetic of
+// quad_hit_masked<0>'s general path, the same products and sums in the same
+// order, and that rejection without the gather of the e21 / e23 tail.
+RTP_DEV bool mesh_tri_hit(const QuadGeom& Q, f3 o, f3 d, float& t_out) {
+  const float dv[3] = {d.x, d.y, d.z};
+  const float P[3] = {cross_c<7, 0>(dv, Q.e03), cross_c<7, 1>(dv, Q.e03), cross_c<7, 2>(dv, Q.e03)};
+  const float det = dot_m<7>(Q.e01, P);
+  const float inv_det = rcp_det(det);
+  const float T[3] = {o.x - Q.vv[0][0], o.y - Q.vv[1][0], o.z - Q.vv[2][0]};
+  const float alpha = dot_m<7>(T, P) * inv_det;
+  const float Qv[3] = {cross_c<7, 0>(T, Q.e01), cross_c<7, 1>(T, Q.e01), cross_c<7, 2>(T, Q.e01)};
+  const float beta = dot_m<7>(dv, Qv) * inv_det;
+  const float t = dot_m<7>(Q.e03, Qv) * inv_det;
+  t_out = t;
+  return !(fabsf(det) < kEps) && !(alpha < 0.0f) && !(beta < 0.0f) && !(t < 0.0f) && !((alpha + beta) > 1.0f);
+}
 // One quad (leaf-order position j) against the closest hit so far; h.kind is
 // -1 (none), 0 (a quad, h.idx its caller's index) or 1 (an inline sphere).
 RTP_DEV void mesh_quad_test(GF4* __restrict__ quads, int j, f3 o, f3 d, Hit& h) {
@@ -252,7 +271,13 @@ RTP_DEV void mesh_quad_test(GF4* __restrict__ quads, int j, f3 o, f3 d, Hit& h) 
   QuadGeom G;
   __builtin_memcpy(&G, hd, sizeof(G));
   float t;
+#if RTP_MESH_TRI_TEST
+  const bool ok = G.kind == kMeshKindTri
+                      ? mesh_tri_hit(G, o, d, t)
+                      : quad_hit_masked<0>(G, *reinterpret_cast<const DevQuad*>((const f4v*)q), o, d, t);
+#else
   const bool ok = quad_hit_masked<0>(G, *reinterpret_cast<const DevQuad*>((const f4v*)q), o, d, t);
+#endif
   const int idx = (int)G.key_lo;
   if (ok && t > 0.001f && (t < h.t || (t == h.t && (h.kind == 1 || (h.kind == 0 && idx < h.idx))))) {
     h.t = t;

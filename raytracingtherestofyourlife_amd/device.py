@@ -13,6 +13,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ErrorBadValue, RtpFfInfo, RtpSceneDesc, RtpStats, RtpView, check, pixel_aux, ptr, render_state
+from .mesh import cell_rows
 
 if TYPE_CHECKING:
     from .mapper import Camera
@@ -53,11 +54,20 @@ def scene_desc(coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_ra
     return d, arrs
 
 
+def mesh_scene_desc(coords, quad_points, *rest, **kw):
+    """scene_desc for a mesh scene (rtp_set_scene_mesh): quad_points may also
+    be [N, 3], triangle cells -- a row (a, b, c) becomes (a, b, c, c)
+    (include/rtp_mesh.h)."""
+    return scene_desc(coords, cell_rows(quad_points), *rest, **kw)
+
+
 class Device:
     """One rtp_context (one HIP device)."""
 
-    def __init__(self, device: int = 0):
-        self._L = _lib.load()
+    def __init__(self, device: int = 0, lib: ctypes.CDLL | None = None):
+        """``lib``: a librtp loaded and bound by the caller (the A/B tools run
+        several builds side by side); None: the in-tree library."""
+        self._L = _lib.load() if lib is None else lib
         h = _lib.vp()
         check(self._L.rtp_create(int(device), h))
         self.handle = h
@@ -93,9 +103,14 @@ class Device:
                        sphere_tex, mat_type, tex_type, tex, light_quad_points=(8, 9, 10, 11), light_sphere_point=48,
                        ior=1.5):
         """rtp_set_scene_mesh: set_scene's arguments, any number of quads up to
-        2^22 behind a BVH in device memory, at most 8 spheres."""
-        d, _arrays = scene_desc(coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius, sphere_mat,
-                                sphere_tex, mat_type, tex_type, tex, light_quad_points, light_sphere_point, ior)
+        2^22 behind a BVH in device memory, at most 8 spheres.  quad_points is
+        [N, 4], or [N, 3] for triangle cells: a row (a, b, c) is the cell
+        (a, b, c, c), which always gets a tight box (rtp.triangulate splits
+        the bent quads of a curved surface; mesh_counts() tells how many
+        cells every ray has to test)."""
+        d, _arrays = mesh_scene_desc(coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius,
+                                     sphere_mat, sphere_tex, mat_type, tex_type, tex, light_quad_points,
+                                     light_sphere_point, ior)
         check(self._L.rtp_set_scene_mesh(self.handle, d))
 
     def set_scene_mesh_device(self, coords, quad_points, quad_mat, quad_tex, sphere_points, sphere_radius, sphere_mat,
@@ -108,9 +123,18 @@ class Device:
         for set_scene_mesh.  ``stream``: a torch stream or a raw hipStream_t
         (None: torch's current stream on this device); the build is queued
         behind the work that produced the tensors there, and the call returns
-        when the scene is in place.  The tensors are not kept."""
+        when the scene is in place.  The tensors are not kept.  quad_points
+        may be int32 [Q, 3]: triangle cells, expanded to (a, b, c, c) with
+        torch on the device, on the build's stream (no host copy)."""
         import torch
 
+        if stream is None:
+            stream = torch.cuda.current_stream(self.device)
+        if isinstance(quad_points, torch.Tensor) and quad_points.dim() == 2 and quad_points.shape[1] == 3 \
+                and quad_points.is_cuda and quad_points.dtype == torch.int32:
+            on = stream if hasattr(stream, "cuda_stream") else torch.cuda.ExternalStream(int(stream), device=self.device)
+            with torch.cuda.stream(on):
+                quad_points = cell_rows(quad_points).contiguous()
         want = (("coords", coords, torch.float32, (None, 3)), ("quad_points", quad_points, torch.int32, (None, 4)),
                 ("quad_mat", quad_mat, torch.int32, (None,)), ("quad_tex", quad_tex, torch.int32, (None,)))
         for name, t, dtype, shape in want:
@@ -134,8 +158,6 @@ class Device:
         d.quad_mat = ctypes.cast(quad_mat.data_ptr(), _lib.i32p)
         d.quad_tex = ctypes.cast(quad_tex.data_ptr(), _lib.i32p)
         d.n_quads = quad_points.shape[0]
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device)
         handle = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
         check(self._L.rtp_set_scene_mesh_device(self.handle, d, handle))
 
@@ -146,6 +168,15 @@ class Device:
         cm, rc = ctypes.c_float(), ctypes.c_float()
         check(self._L.rtp_mesh_guarantee(self.handle, cm, rc))
         return float(cm.value), float(rc.value)
+
+    def mesh_counts(self) -> tuple[int, int, int]:
+        """(cells, triangle cells, cells with an unbounded box) of the current
+        mesh scene (rtp_mesh_counts).  Every ray tests the unbounded ones: a
+        large third number is why a mesh renders slowly, and rtp.triangulate
+        with rtp.unbounded_cells is the remedy."""
+        n, tri, unb = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        check(self._L.rtp_mesh_counts(self.handle, n, tri, unb))
+        return int(n.value), int(tri.value), int(unb.value)
 
     def set_cornell_box(self, variant: int = 0):
         d = RtpSceneDesc()

@@ -15,8 +15,8 @@ fi
 mkdir -p "$(dirname "$out")"
 denoise=$src/rtp_denoise.hip  # (absent in revisions before the denoised previews)
 [ -f "$denoise" ] || denoise=
-more=  # (sources that later revisions added: adaptive passes, the mesh BVH builder)
-for f in rtp_adaptive.hip rtp_adaptive_host.cpp rtp_mesh_host.cpp; do [ -f "$src/$f" ] && more="$more $src/$f"; done
+more=  # (sources that later revisions added: adaptive passes, the mesh BVH builders)
+for f in rtp_adaptive.hip rtp_adaptive_host.cpp rtp_mesh_host.cpp rtp_mesh_gpu.hip; do [ -f "$src/$f" ] && more="$more $src/$f"; done
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -fno-slp-vectorize "$@" \
   -o "$out" "$src"/rtp_kernels.hip "$src"/rtp_direct.hip "$src"/rtp_bvh_gpu.hip $denoise "$src"/rtp_host.cpp \
   "$src"/rtp_direct_host.cpp "$src"/scene_cornell.cpp $more

@@ -5,6 +5,7 @@ tool; its output is profiles/mesh_bench.txt).
 
     python tools/mesh_bench.py [--sizes 1024,16384,262144,1048576] [--reps 10]
         [--nx 512 --ny 512 --spp 16 --depth 50] [--scan-max 16384]
+        [--scene grid|hills|hills_quads]
     RTP_LIB_PATH=variants/mesh_leaf1.so python tools/mesh_bench.py ...   # kMeshLeaf
         (tools/build_variant.sh variants/mesh_leaf1.so -DRTP_MESH_LEAF=1)
 
@@ -15,6 +16,11 @@ the scan finishes in seconds (<= --scan-max quads) a second context holds the
 same scene set under RTP_MESH_SCAN=1 and the two alternate, window by window;
 every side is warmed up first; the report is the median, minimum and maximum
 of --reps windows.  The RNG jump tables are off.  One JSON line per case.
+
+--scene hills: hills(n), the curved terrain of tests/_trimeshes.py at n terrain
+cells, each given as two triangle cells (2 n + 5 cells); hills_quads: the same
+terrain as n bent quads, most of them with the unbounded box (the report's
+"cells", "triangles", "unbounded" are Device.mesh_counts()).
 """
 import argparse
 import ctypes
@@ -32,6 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import torch  # noqa: E402
 
 import _meshes  # noqa: E402  (the generated terrains of the tests)
+import _trimeshes  # noqa: E402
 import raytracingtherestofyourlife_amd as rtp  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -43,6 +50,7 @@ ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--scan-max", type=int, default=16384)
+ap.add_argument("--scene", choices=("grid", "hills", "hills_quads"), default="grid")
 a = ap.parse_args()
 if a.reps < 10:
     ap.error("--reps must be at least 10")
@@ -87,7 +95,7 @@ def alternate(devs):
 
 
 for n in [int(s) for s in a.sizes.split(",") if s]:
-    m = _meshes.grid(n)
+    m = _meshes.grid(n) if a.scene == "grid" else _trimeshes.hills(n, a.scene == "hills")
     t0 = time.perf_counter()
     b = _meshes.build_host(m)
     build_s = time.perf_counter() - t0
@@ -96,7 +104,9 @@ for n in [int(s) for s in a.sizes.split(",") if s]:
     if n <= a.scan_max:
         devs["scan"] = context(lambda d: d.set_scene_mesh(*m.set_args()), scan=True)
     ms = alternate(devs)
-    rep = {"case": f"grid({n})", "quads": len(m.quads), "mesh_leaf": leaf, "host_build_s": round(build_s, 3),
+    # (a baseline library named by RTP_LIB_PATH may be from before rtp_mesh_counts)
+    cells, triangles, unbounded = devs["walk"].mesh_counts() if hasattr(L, "rtp_mesh_counts") else (None, None, None)
+    rep = {"case": f"{a.scene}({n})", "quads": len(m.quads), "triangles": triangles, "unbounded": unbounded, "mesh_leaf": leaf, "host_build_s": round(build_s, 3),
            "nodes_per_octant": nodes, "node_bytes": 8 * 16 * nodes, "quad_bytes": 160 * len(m.quads),
            "nx": a.nx, "ny": a.ny, "spp": a.spp, "depth": a.depth, "reps": a.reps}
     for k, v in ms.items():

@@ -3,8 +3,10 @@ against the host build (rtp_set_scene_mesh) on tools/mesh_bench.py's terrains
 (development tool; its output is profiles/mesh_device_build.txt).
 
     python tools/mesh_build_bench.py [--sizes 1024,16384,262144,1048576] [--reps 10]
-        [--nx 512 --ny 512 --spp 16 --depth 50]
+        [--nx 512 --ny 512 --spp 16 --depth 50] [--scene grid|hills|hills_quads]
 
+--scene hills: hills(n), the curved terrain of tests/_trimeshes.py at n terrain
+cells as 2 n triangle cells; hills_quads: the same terrain as n bent quads.
 Per size, one JSON line:
   build wall time (ms) of (a) rtp_set_scene_mesh from host arrays -- host build
   plus upload -- and (b) rtp_set_scene_mesh_device from tensors already on the
@@ -31,6 +33,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import _meshes  # noqa: E402  (the generated terrains of the tests)
+import _trimeshes  # noqa: E402
 import raytracingtherestofyourlife_amd as rtp  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -41,6 +44,7 @@ ap.add_argument("--spp", type=int, default=16)
 ap.add_argument("--depth", type=int, default=50)
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--warmup", type=int, default=2)
+ap.add_argument("--scene", choices=("grid", "hills", "hills_quads"), default="grid")
 a = ap.parse_args()
 if a.reps < 10:
     ap.error("--reps must be at least 10")
@@ -69,7 +73,7 @@ def kernel_ms(dev):
 
 
 for n in [int(s) for s in a.sizes.split(",") if s]:
-    m = _meshes.grid(n)
+    m = _meshes.grid(n) if a.scene == "grid" else _trimeshes.hills(n, a.scene == "hills")
     args = m.set_args()
     tens = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (m.points, m.quads, m.quad_mat, m.quad_tex)]
     torch.cuda.synchronize()
@@ -96,7 +100,8 @@ for n in [int(s) for s in a.sizes.split(",") if s]:
     for _ in range(a.reps):
         for k, d in devs.items():
             ms[k].append(kernel_ms(d))
-    rep = {"case": f"grid({n})", "quads": len(m.quads), "nx": a.nx, "ny": a.ny, "spp": a.spp, "depth": a.depth,
+    rep = {"case": f"{a.scene}({n})", "quads": len(m.quads), "counts_host": devs["host"].mesh_counts(),
+           "counts_device": devs["device"].mesh_counts(), "nx": a.nx, "ny": a.ny, "spp": a.spp, "depth": a.depth,
            "reps": a.reps}
     for k in builders:
         rep[k + "_build_ms"] = summary(wall[k])

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "librtp.so")
 SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_mesh_gpu.hip", "rtp_denoise.hip", "rtp_adaptive.hip", "rtp_host.cpp", "rtp_direct_host.cpp", "rtp_adaptive_host.cpp", "rtp_mesh_host.cpp",
            "scene_cornell.cpp"]
-HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "rtp_adaptive.hpp", "rtp_bvh_host.hpp", "rtp_mesh.hpp", "rtp_mesh_gpu.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
+HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_util.hpp", "rtp_adaptive.hpp", "rtp_bvh_host.hpp", "rtp_mesh.hpp", "rtp_mesh_gpu.hpp", "rtp_mesh_cell.hpp", "rtp_lbvh.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
            os.path.join("..", "..", "include", "rtp_adaptive.h"), os.path.join("..", "..", "include", "rtp_mesh.h")]
 ARCH = os.environ.get("RTP_OFFLOAD_ARCH", "gfx950")
 
@@ -90,6 +90,24 @@ def build_cpp(force: bool = False) -> list[str]:
     return built
 
 
+# The per-cell maths of the mesh builders (csrc/rtp_mesh_cell.hpp) as host C++
+# with its own main: no HIP, no librtp.so (tests/test_mesh_cell.py).
+MESH_CELL_CHECK = os.path.join(ROOT, "tests", "cpp", "mesh_cell_check")
+
+
+def build_mesh_cell_check(force: bool = False) -> str:
+    src = MESH_CELL_CHECK + ".cpp"
+    deps = [src, os.path.join(CSRC, "rtp_mesh_cell.hpp"), os.path.join(CSRC, "rtp_layout.hpp")]
+    if force or not os.path.exists(MESH_CELL_CHECK) or any(os.path.getmtime(d) > os.path.getmtime(MESH_CELL_CHECK)
+                                                            for d in deps):
+        cmd = [hipcc(), "-x", "c++", "-O2", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-I", CSRC,
+               src, "-o", MESH_CELL_CHECK]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        if res.returncode != 0:
+            raise RuntimeError(f"hipcc -x c++ failed for {src}:\n{res.stderr}")
+    return MESH_CELL_CHECK
+
+
 # The reference's own main.cc and CornellBox.cpp, compiled UNCHANGED against
 # librtp.so through the VTK-m-named headers of include/vtkm_compat
 # (rtp/vtkm_compat.hpp).  The recipe is oracle/ref_build.py; its objects and
@@ -131,6 +149,7 @@ ASAN_PROGRAMS = {
     os.path.join(ASAN_DIR, "asan_adaptive"): os.path.join(ROOT, "tests", "cpp", "asan_adaptive.cpp"),
     os.path.join(ASAN_DIR, "asan_mesh"): os.path.join(ROOT, "tests", "cpp", "asan_mesh.cpp"),
     os.path.join(ASAN_DIR, "asan_mesh_tri"): os.path.join(ROOT, "tests", "cpp", "asan_mesh_tri.cpp"),
+    os.path.join(ASAN_DIR, "mesh_cell_check"): os.path.join(ROOT, "tests", "cpp", "mesh_cell_check.cpp"),
 }
 # AddressSanitizer + UBSan on host code only (GPU sanitizers are not available
 # on the pool): each -fsanitize= directly after -Xarch_host.  The sanitizer
@@ -160,13 +179,15 @@ def build_asan(force: bool = False) -> list[str]:
     inc = os.path.join(ROOT, "include")
     built = []
     for exe, src in ASAN_PROGRAMS.items():
+        if not os.path.exists(src):
+            continue  # a tests/ tree without this driver: the others still build; its test finds no program
         deps = objs + [src, os.path.join(inc, "rtp.h"), os.path.join(inc, "rtp_adaptive.h"),
                        os.path.join(inc, "rtp", "rendering.hpp")]
         if force or not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
             # the driver is host C++ (g++-style, like build_cpp), the link
             # pulls in the HIP runtime and the static sanitizer runtimes
-            res = subprocess.run([*base, "-x", "c++", "-I", inc, "-c", src, "-o", exe + ".o"], capture_output=True,
-                                 text=True)
+            res = subprocess.run([*base, "-x", "c++", "-I", inc, "-I", CSRC, "-c", src, "-o", exe + ".o"],
+                                 capture_output=True, text=True)
             if res.returncode == 0:
                 res = subprocess.run([hipcc(), "-fsanitize=address,undefined", exe + ".o", *objs, "-o", exe],
                                      capture_output=True, text=True)
@@ -179,4 +200,5 @@ def build_asan(force: bool = False) -> list[str]:
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print("\n".join(build_cpp(force="--force" in sys.argv)))
+    print(build_mesh_cell_check(force="--force" in sys.argv))
     print(build_main_unchanged(force="--force" in sys.argv))

@@ -3,7 +3,8 @@
 // SphereIntersector.cxx:46-76 / AABBSurface.h), for scenes too large for the
 // host's binned-SAH build in rtp_host.cpp.
 //
-// Linear BVH (Karras 2012) over the sphere centres:
+// Linear BVH (Karras 2012; the radix tree and the octant climb are
+// rtp_lbvh.hpp's, shared with the mesh builder) over the sphere centres:
 //   1. 30-bit Morton code of each centre in the centres' bounding box;
 //   2. sort (code, sphere) pairs with rocPRIM's radix sort (hipCUB);
 //   3. one thread per internal node finds its key range and split (duplicate
@@ -24,18 +25,11 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rtp_layout.hpp"
+#include "rtp_lbvh.hpp"
+#include "rtp_mesh_cell.hpp"
 
 namespace rtp {
 namespace {
-
-// spread the low 10 bits of v to every third bit
-__device__ __forceinline__ uint32_t expand_bits(uint32_t v) {
-  v = (v * 0x00010001u) & 0xFF0000FFu;
-  v = (v * 0x00000101u) & 0x0F00F00Fu;
-  v = (v * 0x00000011u) & 0xC30C30C3u;
-  v = (v * 0x00000005u) & 0x49249249u;
-  return v;
-}
 
 __global__ void k_morton(const float4* __restrict__ cr, int n, float3 lo, float3 inv_ext, uint32_t* __restrict__ code,
                          uint32_t* __restrict__ idx) {
@@ -48,46 +42,16 @@ __global__ void k_morton(const float4* __restrict__ cr, int n, float3 lo, float3
   idx[i] = (uint32_t)i;
 }
 
-// common-prefix length of sorted keys i and j (-1 outside); equal codes
-// compare their positions, so every key is distinct
-__device__ __forceinline__ int delta(const uint32_t* __restrict__ code, int n, int i, int j) {
-  if (j < 0 || j >= n) return -1;
-  const uint32_t a = code[i], b = code[j];
-  if (a != b) return __clz(a ^ b);
-  return 32 + __clz((uint32_t)i ^ (uint32_t)j);
-}
-
 // Node ids: internal nodes 0..n-2 (root 0), leaf j (sorted position) = n-1+j.
 __global__ void k_karras(const uint32_t* __restrict__ code, int n, int2* __restrict__ child,
                          int* __restrict__ parent, int8_t* __restrict__ axis) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n - 1) return;
-  const int d = (delta(code, n, i, i + 1) - delta(code, n, i, i - 1)) >= 0 ? 1 : -1;
-  const int dmin = delta(code, n, i, i - d);
-  int lmax = 2;
-  while (delta(code, n, i, i + lmax * d) > dmin) lmax <<= 1;
-  int l = 0;
-  for (int t = lmax >> 1; t >= 1; t >>= 1)
-    if (delta(code, n, i, i + (l + t) * d) > dmin) l += t;
-  const int j = i + l * d;
-  const int dnode = delta(code, n, i, j);
-  int s = 0;
-  for (int div = 2;; div <<= 1) {
-    const int t = (l + div - 1) / div;
-    if (delta(code, n, i, i + (s + t) * d) > dnode) s += t;
-    if (t == 1) break;
-  }
-  const int gamma = i + s * d + min(d, 0);
-  const int first = min(i, j), last = max(i, j);
-  const int left = (first == gamma) ? (n - 1 + gamma) : gamma;
-  const int right = (last == gamma + 1) ? (n - 1 + gamma + 1) : gamma + 1;
-  child[i] = make_int2(left, right);
-  parent[left] = i;
-  parent[right] = i;
-  // split axis: the Morton bit the range splits on (x at bits 3k+2, y 3k+1,
-  // z 3k); ranges of equal codes split by position: x
-  const int bit = 31 - dnode;
-  axis[i] = (int8_t)(dnode >= 32 ? 0 : (bit % 3 == 2 ? 0 : (bit % 3 == 1 ? 1 : 2)));
+  const KarrasNode k = karras_node(code, n, i);
+  child[i] = make_int2(k.left, k.right);
+  parent[k.left] = i;
+  parent[k.right] = i;
+  axis[i] = (int8_t)k.axis;
   if (i == 0) parent[0] = -1;
 }
 
@@ -129,13 +93,9 @@ __global__ void k_flatten(const float4* __restrict__ cr, const uint32_t* __restr
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (int64_t)nn * 8) return;
   const int oct = (int)(g / nn), x = (int)(g % nn);
-  int pos = 0;
-  for (int c = x, p = parent[x]; p >= 0; c = p, p = parent[p]) {
-    const int2 ch = child[p];
-    const bool neg = (oct >> axis[p]) & 1;  // moving toward lower coordinates: right (upper) child first
-    const int near = neg ? ch.y : ch.x;
-    pos += (c == near) ? 1 : 1 + size[near];
-  }
+  int at[1];
+  octant_positions(x, oct, child, parent, axis, size, at);
+  const int pos = at[0];
   BvhNode nd;
   nd.skip = pos + size[x];
   if (x >= n - 1) {  // leaf: the sphere itself
@@ -166,11 +126,6 @@ __global__ void k_geom(const float4* __restrict__ cr, const uint32_t* __restrict
   g.orig = (int32_t)idx[j];
   g.pad[0] = g.pad[1] = g.pad[2] = 0;
   geom[j] = g;
-}
-
-template <typename T>
-hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
 }
 
 }  // namespace
@@ -245,21 +200,6 @@ extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, fl
 
 namespace rtp {
 namespace {
-// f32 -> f16 bits rounded outward: the nearest half, then stepped toward
-// -inf (down) or +inf (up) until its value (decoded by the same instruction
-// the walk uses) is on the right side of x; if that fails, an infinity.
-__device__ uint32_t half_outward(float x, bool up) {
-  uint32_t b = __builtin_bit_cast(uint16_t, (_Float16)x);
-  for (int i = 0; i < 4; i++) {
-    const float v = (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-    if (up ? v >= x : v <= x) return b;
-    const bool neg = (b & 0x8000u) != 0, zero = (b & 0x7fffu) == 0;
-    if (zero) b = up ? 0x0001u : 0x8001u;
-    else if (up) b = neg ? b - 1 : b + 1;
-    else b = neg ? b + 1 : b - 1;
-  }
-  return up ? 0x7c00u : 0xfc00u;
-}
 __global__ void k_compact(const BvhNode* __restrict__ nodes, int64_t total, uint32_t* __restrict__ cn,
                           int32_t* __restrict__ cidx) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -79,39 +79,6 @@ uint32_t which_threshold(int w) {
   return lo > 0xffffffffull ? 0xffffffffu : (uint32_t)lo;
 }
 
-void fill_quad(rtp::DevQuad& Q, v3 q, v3 r, v3 s, v3 t) {
-  std::memset(&Q, 0, sizeof(Q));
-  for (int k = 0; k < 3; k++) Q.vv[k][0] = (&q.x)[k], Q.vv[k][1] = (&s.x)[k];
-  st(Q.e01, sub(r, q));
-  st(Q.e03, sub(t, q));
-  st(Q.e21, sub(r, s));
-  st(Q.e23, sub(t, s));
-  st(Q.n, normalize(cross(sub(r, q), sub(s, q))));  // TriangleNormal(q,r,s), Surface.h:182-183
-  // zero-structure kind (exact zeros only; see quad_hit_masked)
-  auto mask_of = [](const float* e) {
-    int m = 0;
-    for (int k = 0; k < 3; k++)
-      if (e[k] != 0.0f) m |= 1 << k;
-    return m;
-  };
-  const int m01 = mask_of(Q.e01), m03 = mask_of(Q.e03), m21 = mask_of(Q.e21), m23 = mask_of(Q.e23);
-  // exact parallelogram (see quad_hit_masked): value equality; the sign of a
-  // zero component only ever changes the sign of a zero intermediate
-  Q.para = 1;
-  for (int k = 0; k < 3; k++)
-    if (!(-Q.e01[k] == Q.e23[k] && -Q.e03[k] == Q.e21[k])) Q.para = 0;
-  Q.kind = 0;
-  for (int k = 1; k < rtp::kQuadKinds; k++) {
-    const rtp::QuadKindMasks& K = rtp::kQuadKind[k];
-    if (K.m01 == m01 && K.m03 == m03 && K.m21 == m21 && K.m23 == m23) Q.kind = k;
-  }
-  // Kinds 1..6 are axis-plane rectangles: their masks force s = (r_I, t_J),
-  // so e23 == -e01 and e21 == -e03 exactly and they are always exact
-  // parallelograms (the prefilter's exact test, quad_hit_axis, relies on it;
-  // setup_prefilter re-checks Q.para).  An in-plane quad that is not a
-  // parallelogram has a non-rectangular mask set and is kind 0.
-}
-
 bool bit_equal(const float* a, const float* b, int n) { return std::memcmp(a, b, sizeof(float) * n) == 0; }
 
 // Closest-hit prefilter tables (rtp_kernels.hip closest_hit):
@@ -138,7 +105,7 @@ void setup_prefilter(rtp::DevScene* h, const rtp_scene_desc* s, const std::vecto
     const int flat = 7 & ~(K.m01 | K.m03);
     if (Q.kind < 1 || Q.kind > 6 || (flat != 1 && flat != 2 && flat != 4)) return;
     const int a = flat == 1 ? 0 : flat == 2 ? 1 : 2, b = (a + 1) % 3, c = (a + 2) % 3;
-    if (!Q.para) return;  // (unreachable: kinds 1..6 are exact parallelograms, see fill_quad)
+    if (!Q.para) return;  // (unreachable: kinds 1..6 are exact parallelograms, see mesh_cell_record)
     {
       const int ei = K.m01 == 1 ? 0 : K.m01 == 2 ? 1 : 2, ej = K.m03 == 1 ? 0 : K.m03 == 2 ? 1 : 2;
       const int ea = 3 - ei - ej;
@@ -533,6 +500,14 @@ struct SceneBuild {
   // or, built on the device (rtp_mesh_gpu.hip): the arrays themselves, which scene_upload adopts
   bool mesh_on_device = false;
   rtp::MeshGpuOut mesh_dev;
+
+  // the host image zeroed, every octant its own walk order (the device LBVH
+  // build keeps all 8; the host SAH build may narrow it, RTP_BVH_OCT_MASK)
+  rtp::DevScene* fresh() {
+    std::memset(h.get(), 0, sizeof(*h));
+    h->oct_mask = 7;
+    return h.get();
+  }
 };
 
 // (pt_ok, mat_ok, tex_ok: rtp_host_util.hpp, shared with the mesh builder)
@@ -549,11 +524,7 @@ rtp_status scene_quads(const rtp_scene_desc* s, SceneBuild& B) {
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: bad primitive counts");
   if (s->n_spheres < 1)
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: the light sphere radius is SphereRadii[0]; need >= 1 sphere");
-  rtp::DevScene* h = B.h.get();
-  std::memset(h, 0, sizeof(*h));
-  // (after the memset: every octant its own walk order -- the device LBVH
-  // build keeps all 8; the host SAH build may narrow it, RTP_BVH_OCT_MASK)
-  h->oct_mask = 7;
+  rtp::DevScene* h = B.fresh();
   std::vector<int>& kept = B.kept;
   std::vector<rtp::DevQuad> built;
   for (int q = 0; q < s->n_quads; q++) {
@@ -576,8 +547,7 @@ rtp_status scene_quads(const rtp_scene_desc* s, SceneBuild& B) {
     if ((int)kept.size() >= rtp::kMaxQuads)
       return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: too many distinct quads");
     rtp::DevQuad Q;
-    fill_quad(Q, ld(s->points + 3 * id[0]), ld(s->points + 3 * id[1]), ld(s->points + 3 * id[2]),
-              ld(s->points + 3 * id[3]));
+    fill_quad(Q, s->points + 3 * id[0], s->points + 3 * id[1], s->points + 3 * id[2], s->points + 3 * id[3], false);
     Q.mt = s->mat_type[s->quad_mat[q]];
     st(Q.alb, ld(s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]]));
     Q.orig = (int32_t)kept.size();  // rank in the reference's (index) order
@@ -659,19 +629,10 @@ rtp_status scene_spheres(const rtp_scene_desc* s, SceneBuild& B) {
   // The reach of the sphere boxes' pad (rtp_layout.hpp bvh_sphere_pad):
   // kBvhReachFactor diagonals of the scene's bounding box -- every quad
   // vertex, every sphere's c -+ r.
-  float& bvh_reach = B.bvh_reach;
   if (use_bvh) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int q = 0; q < s->n_quads; q++)
-      for (int c2 = 0; c2 < 4; c2++)
-        for (int k = 0; k < 3; k++) {
-          const float v = s->points[3 * s->quad_points[4 * q + c2] + k];
-          lo[k] = std::min(lo[k], v), hi[k] = std::max(hi[k], v);
-        }
-    for (const rtp::DevSphere& S : sph)
-      for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], S.c[k] - S.r), hi[k] = std::max(hi[k], S.c[k] + S.r);
-    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-    bvh_reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
+    scene_bounds(s, true, lo, hi);
+    B.bvh_reach = rtp::scene_reach(lo, hi);
   }
   // which builder makes the sphere BVH: the host's binned SAH (better trees,
   // O(n log n) on one core) or the device LBVH (rtp_bvh_gpu.hip) for large
@@ -785,7 +746,7 @@ rtp_status scene_lights(const rtp_scene_desc* s, SceneBuild& B) {
     return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light sphere point id out of range");
   v3 q = ld(s->points + 3 * lq[0]), r = ld(s->points + 3 * lq[1]), ss = ld(s->points + 3 * lq[2]),
      t = ld(s->points + 3 * lq[3]);
-  fill_quad(h->light.quad, q, r, ss, t);
+  fill_quad(h->light.quad, &q.x, &r.x, &ss.x, &t.x, false);
   {
     float qr = std::sqrt(dot(sub(r, q), sub(r, q)));  // vtkm::Magnitude
     float qt = std::sqrt(dot(sub(t, q), sub(t, q)));
@@ -1010,24 +971,17 @@ rtp_status set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, hipStr
   hs.n_points = ns + 5;
   hs.sphere_point = sphere_point;
   hs.quad_points = hs.quad_mat = hs.quad_tex = nullptr;
-  // the reach: mesh_build's expression over the device's exact min / max and the spheres' c -+ r
+  // the reach: mesh_build's, over the device's exact min / max of the quads' vertices and the spheres' c -+ r
   SceneBuild B;
   B.mesh = true;
   {
     float lo[3], hi[3];
     for (int k = 0; k < 3; k++) lo[k] = rtp::mesh_key_float(info.lo[k]), hi[k] = rtp::mesh_key_float(info.hi[k]);
-    for (int j = 0; j < ns; j++)
-      for (int k = 0; k < 3; k++) {
-        const float cc = pts[3 * j + k], r = s->sphere_radius[j];
-        lo[k] = std::min(lo[k], cc - r), hi[k] = std::max(hi[k], cc + r);
-      }
-    const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-    B.mb.reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
-    if (!std::isfinite(B.mb.reach)) return mesh_bounds_fail();
+    scene_bounds(&hs, false, lo, hi);
+    B.mb.reach = rtp::scene_reach(lo, hi);
+    if (!rtp::finite_f(B.mb.reach)) return mesh_bounds_fail();
   }
-  rtp::DevScene* h = B.h.get();
-  std::memset(h, 0, sizeof(*h));
-  h->oct_mask = 7;
+  rtp::DevScene* h = B.fresh();
   RTP_TRY(scene_spheres(&hs, B));
   scene_sphere_bvh(&hs, B);
   RTP_TRY(scene_lights(&hs, B));
@@ -1092,36 +1046,15 @@ rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
   SceneBuild B;
   B.mesh = true;
   RTP_TRY(mesh_build(s, B.mb));
-  rtp::DevScene* h = B.h.get();
-  std::memset(h, 0, sizeof(*h));
-  h->oct_mask = 7;
+  rtp::DevScene* h = B.fresh();
   RTP_TRY(scene_spheres(s, B));  // (fewer than kBvhMinSpheres: no sphere BVH)
   scene_sphere_bvh(s, B);
   RTP_TRY(scene_lights(s, B));
-  const int n = s->n_quads;
-  B.mesh_quads.resize(n);
-  B.mesh_shade.assign((size_t)8 * n, 0.f);
-  for (int j = 0; j < n; j++) {
-    const int q = B.mb.order[j];
-    const int32_t* id = s->quad_points + 4 * q;
-    rtp::DevQuad& Q = B.mesh_quads[j];
-    fill_quad(Q, ld(s->points + 3 * id[0]), ld(s->points + 3 * id[1]), ld(s->points + 3 * id[2]),
-              ld(s->points + 3 * id[3]));
-    // a triangle cell's mark, in the mesh record only (rtp_trace.hpp mesh_quad_test)
-    if (rtp::mesh_is_triangle(s->points + 3 * id[2], s->points + 3 * id[3])) Q.kind = rtp::kMeshKindTri;
-    Q.mt = s->mat_type[s->quad_mat[q]];
-    st(Q.alb, ld(s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]]));
-    Q.orig = q;
-    Q.key_lo = (uint32_t)q;  // the caller's index: the hit's index and the tie-break of equal t
-    float* sh = B.mesh_shade.data() + (size_t)8 * q;
-    std::memcpy(sh, Q.n, 12);
-    std::memcpy(sh + 3, Q.alb, 12);
-    std::memcpy(sh + 6, &Q.mt, 4);
-  }
+  mesh_records(s, B.mb, B.mesh_quads, B.mesh_shade);
   B.mesh_cnodes.resize((size_t)4 * B.mb.nodes.size());
   mesh_compact(B.mb.nodes.data(), (int64_t)B.mb.nodes.size(), B.mesh_cnodes.data());
   h->n_mesh_nodes = B.mb.n_nodes;
-  h->n_mesh_quads = n;
+  h->n_mesh_quads = s->n_quads;
   h->mesh_scan = env_is("RTP_MESH_SCAN", '1') ? 1 : 0;
   for (int k = 0; k < 3; k++) B.blo[k] = 0.f, B.bhi[k] = 0.f;  // (-direct mode is refused on a mesh scene)
   return scene_upload(c, s, B);

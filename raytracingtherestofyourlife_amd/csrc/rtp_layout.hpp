@@ -156,7 +156,7 @@ inline float bvh_sphere_pad(float cx, float cy, float cz, float r, float reach) 
   return slab + (__builtin_sqrtf(r * r + E) - r) + kBvhReachRound * reach;
 }
 
-// The pad of a mesh quad's box (rtp_mesh_host.cpp; the walk: rtp_trace.hpp
+// The pad of a mesh quad's box (rtp_mesh_cell.hpp; the walk: rtp_trace.hpp
 // mesh_visit).  As for the spheres the boxes only cull, which is sound only
 // if every ray that the float32 quad test (quad_hit_masked<0>) accepts for a
 // quad crosses every box around it with the point at the accepted t inside.

@@ -6,6 +6,7 @@
 
 #include "../../include/rtp_mesh.h"
 #include "rtp_layout.hpp"
+#include "rtp_mesh_cell.hpp"
 
 namespace rtp_host {
 
@@ -34,6 +35,17 @@ rtp_status mesh_bounds_fail();
 rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& out, int leaf_size = rtp::kMeshLeaf);
 // BvhNodes -> the walk's 16-byte compact nodes (half-precision boxes rounded outward)
 void mesh_compact(const rtp::BvhNode* nodes, int64_t total, uint32_t* out);
+// One quad's DevQuad geometry (rtp_mesh_cell.hpp mesh_cell_record; the rest
+// zeroed), for the inline scene and the light quad (mesh = false) and for
+// mesh_records (true: a triangle cell is marked).
+void fill_quad(rtp::DevQuad& Q, const float* q, const float* r, const float* s, const float* t, bool mesh);
+// The records a host-built mesh scene is uploaded as: quads, one per quad in
+// the build's leaf order, and shade, 8 floats per quad in the caller's order.
+void mesh_records(const rtp_scene_desc* s, const MeshBuild& build, std::vector<rtp::DevQuad>& quads,
+                  std::vector<float>& shade);
+// Grows the box (lo, hi) by every quad vertex (quads) and by every sphere's
+// c -+ r: the scene bounds whose diagonals are the reach (scene_reach).
+void scene_bounds(const rtp_scene_desc* s, bool quads, float lo[3], float hi[3]);
 
 }  // namespace rtp_host
 

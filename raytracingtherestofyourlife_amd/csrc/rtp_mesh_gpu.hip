@@ -4,9 +4,9 @@
 //
 //   1. k_validate   mesh_validate's per-quad checks (the first failure by
 //                   lowest quad index) and the min / max of the vertices;
-//   2. k_boxes      each quad's pad (double, quad_pad's operations; tri_pad's
-//                   for a triangle cell, v11 == v01), padded box and box
-//                   centre; the centres' bounds; the counts of rtp_mesh_counts;
+//   2. k_boxes      each quad's pad, padded box and box centre
+//                   (rtp_mesh_cell.hpp mesh_cell_box, the host builder's own
+//                   function); the centres' bounds; the counts of rtp_mesh_counts;
 //   3. k_morton     30-bit Morton code of the centre, bit 30 for a quad with
 //                   the unbounded box: those sort behind all others and the
 //                   radix tree splits them off near its root;
@@ -25,10 +25,12 @@
 //   9. k_quads      the DevQuad record of each quad, computed in leaf order
 //                   and written with 16-byte stores, and its mesh_shade row.
 //
-// Everything a pixel depends on (edges, normal, albedo) repeats fill_quad's
-// float operations in its order with correctly rounded sqrt and division and
-// no contraction, so the records equal the host's bit for bit; so do the pads
-// (IEEE double add, multiply, divide and sqrt) and the boxes.
+// Everything a pixel depends on (edges, normal, albedo) and every pad and box
+// comes from the functions of rtp_mesh_cell.hpp that the host builder calls,
+// compiled here with correctly rounded sqrt and division and no contraction,
+// so the records, pads and boxes equal the host's bit for bit.  What is left
+// here is the device's own: atomics, LDS bounds, 16-byte stores.  The radix
+// tree and the octant climb are rtp_lbvh.hpp's, shared with rtp_bvh_gpu.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -36,6 +38,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include "rtp_layout.hpp"
+#include "rtp_lbvh.hpp"
+#include "rtp_mesh_cell.hpp"
 #include "rtp_mesh_gpu.hpp"
 
 #pragma clang fp contract(off)
@@ -50,91 +54,8 @@ constexpr int kMaxRounds = 31 + 22;
 constexpr int kNotEmitted = -2, kPending = -1;
 
 // ------------------------------------------------------------- helpers ---
-__device__ __forceinline__ uint32_t float_key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : b | 0x80000000u;
-}
-__device__ __forceinline__ float key_float(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-// std::min / std::max as the host's compile evaluates them (the sign of a zero)
-__device__ __forceinline__ float hmin(float a, float b) { return (b < a) ? b : a; }
-__device__ __forceinline__ float hmax(float a, float b) { return (a < b) ? b : a; }
-__device__ __forceinline__ double hmind(double a, double b) { return (b < a) ? b : a; }
-__device__ __forceinline__ double hmaxd(double a, double b) { return (a < b) ? b : a; }
-// std::nextafter(x, +inf) and (x, -inf) of a float that is not NaN
-__device__ __forceinline__ float next_up(float x) {
-  const uint32_t b = __float_as_uint(x);
-  if ((b & 0x7fffffffu) == 0) return __uint_as_float(1u);
-  if (b == 0x7f800000u) return x;
-  return __uint_as_float((b & 0x80000000u) ? b - 1 : b + 1);
-}
-__device__ __forceinline__ float next_down(float x) { return -next_up(-x); }
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool finite_d(double x) {
-  return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
-struct f3 {
-  float x, y, z;
-};
-__device__ __forceinline__ f3 sub(f3 a, f3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ float dot(f3 a, f3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ f3 cross(f3 a, f3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-struct d3 {
-  double x, y, z;
-};
-__device__ __forceinline__ d3 subd(d3 a, d3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ double dotd(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ d3 crossd(d3 a, d3 b) {
-  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ double lend(d3 a) { return sqrt(dotd(a, a)); }
-__device__ __forceinline__ d3 todouble(f3 a) { return {a.x, a.y, a.z}; }
-
 __device__ __forceinline__ f3 load_point(const float* __restrict__ points, int32_t id) {
-  const float* p = points + 3 * (int64_t)id;
-  return {p[0], p[1], p[2]};
-}
-
-// rtp_mesh_host.cpp quad_pad, operation for operation
-__device__ float quad_pad(d3 q, d3 r, d3 s, d3 t, double reach, double amax) {
-  const d3 e01 = subd(r, q), e03 = subd(t, q), e21 = subd(r, s), e23 = subd(t, s);
-  const d3 n1 = crossd(e01, e03);
-  const double A1 = lend(n1), A2 = lend(crossd(e21, e23));
-  const double l1 = lend(e01) * lend(e03), l2 = lend(e21) * lend(e23);
-  if (!(A1 > 0) || !(A2 > 0) || !finite_d(A1) || !finite_d(A2)) return kMeshHuge;
-  const double sine = hmind(A1 / l1, A2 / l2);
-  if (!(sine >= kMeshMinSine)) return kMeshHuge;
-  const double h = fabs(dotd(subd(s, q), n1)) / A1;
-  if (h > 0) {
-    const d3 diag = subd(t, r);
-    const d3 u1 = crossd(n1, diag);
-    const double lu = lend(u1);
-    if (!(lu > 0)) return kMeshHuge;
-    const double side = dotd(subd(q, r), u1) < 0 ? 1.0 : -1.0;
-    const double w = side * dotd(subd(s, r), u1) / lu;
-    if (!(w > 0) || !(h / w < 0.5 * kMeshCosMin)) return kMeshHuge;
-  }
-  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
-  const double pad = ((double)kMeshRound * reach / sine + h) / (double)kMeshCosMin + slab;
-  if (!(pad < reach)) return kMeshHuge;
-  return next_up((float)pad);
-}
-// rtp_mesh_host.cpp tri_pad, operation for operation
-__device__ float tri_pad(d3 q, d3 r, d3 t, double reach, double amax) {
-  const d3 e01 = subd(r, q), e03 = subd(t, q);
-  const double A1 = lend(crossd(e01, e03));
-  const double l1 = lend(e01) * lend(e03);
-  if (!(A1 > 0) || !finite_d(A1)) return kMeshHuge;
-  const double sine = A1 / l1;
-  if (!(sine >= kMeshMinSine)) return kMeshHuge;
-  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
-  const double pad = ((double)kMeshRound * reach / sine) / (double)kMeshCosMin + slab;
-  if (!(pad < reach)) return kMeshHuge;
-  return next_up((float)pad);
+  return load_f3(points + 3 * (int64_t)id);
 }
 
 // a block's min / max of three floats per thread into six global keys
@@ -146,9 +67,9 @@ __device__ __forceinline__ void bounds_init(BlockBounds& s) {
   __syncthreads();
 }
 __device__ __forceinline__ void bounds_add(BlockBounds& s, f3 v) {
-  atomicMin(&s.lo[0], float_key(v.x)), atomicMax(&s.hi[0], float_key(v.x));
-  atomicMin(&s.lo[1], float_key(v.y)), atomicMax(&s.hi[1], float_key(v.y));
-  atomicMin(&s.lo[2], float_key(v.z)), atomicMax(&s.hi[2], float_key(v.z));
+  atomicMin(&s.lo[0], mesh_float_key(v.x)), atomicMax(&s.hi[0], mesh_float_key(v.x));
+  atomicMin(&s.lo[1], mesh_float_key(v.y)), atomicMax(&s.hi[1], mesh_float_key(v.y));
+  atomicMin(&s.lo[2], mesh_float_key(v.z)), atomicMax(&s.hi[2], mesh_float_key(v.z));
 }
 __device__ __forceinline__ void bounds_flush(BlockBounds& s, uint32_t* lo, uint32_t* hi) {
   __syncthreads();
@@ -201,34 +122,16 @@ __global__ void k_boxes(MeshGpuIn in, float reach, float* __restrict__ boxes, fl
   if (q < in.n_quads) {
     f3 v[4];
     for (int k = 0; k < 4; k++) v[k] = load_point(in.points, in.quad_points[4 * (int64_t)q + k]);
-    const bool tri = mesh_is_triangle(&v[2].x, &v[3].x);
-    float mn[3], mx[3];
+    const MeshCellBox c = mesh_cell_box(v[0], v[1], v[2], v[3], reach);
+    pads[q] = c.pad;
+    if (c.tri) atomicAdd(&counts[0], 1u);
+    if (c.pad == kMeshHuge) atomicAdd(&counts[1], 1u);
     for (int k = 0; k < 3; k++) {
-      const float a = (&v[0].x)[k], b = (&v[1].x)[k], c = (&v[2].x)[k], d = (&v[3].x)[k];
-      if (tri) {  // a triangle cell: its three vertices
-        mn[k] = hmin(hmin(a, b), d);
-        mx[k] = hmax(hmax(a, b), d);
-        continue;
-      }
-      const float far = a + (b - a) + (d - a);  // v00 + e01 + e03 with the records' float edges
-      mn[k] = hmin(hmin(hmin(a, b), hmin(c, d)), far);
-      mx[k] = hmax(hmax(hmax(a, b), hmax(c, d)), far);
+      boxes[6 * (int64_t)q + k] = c.lo[k];
+      boxes[6 * (int64_t)q + 3 + k] = c.hi[k];
+      cen[3 * (int64_t)q + k] = c.cen[k];
     }
-    double amax = 0;
-    for (int k = 0; k < 3; k++) amax = hmaxd(amax, (double)hmax(fabsf(mn[k]), fabsf(mx[k])));
-    const float pad = tri ? tri_pad(todouble(v[0]), todouble(v[1]), todouble(v[3]), reach, amax)
-                          : quad_pad(todouble(v[0]), todouble(v[1]), todouble(v[2]), todouble(v[3]), reach, amax);
-    pads[q] = pad;
-    if (tri) atomicAdd(&counts[0], 1u);
-    if (pad == kMeshHuge) atomicAdd(&counts[1], 1u);
-    f3 c;
-    for (int k = 0; k < 3; k++) {
-      boxes[6 * (int64_t)q + k] = next_down(mn[k] - pad);
-      boxes[6 * (int64_t)q + 3 + k] = next_up(mx[k] + pad);
-      (&c.x)[k] = 0.5f * mn[k] + 0.5f * mx[k];
-      cen[3 * (int64_t)q + k] = (&c.x)[k];
-    }
-    bounds_add(sb, c);
+    bounds_add(sb, load_f3(c.cen));
   }
   bounds_flush(sb, info->clo, info->chi);  // (its barrier also closes this block's counts)
   if (threadIdx.x == 0 && counts[0]) atomicAdd(&info->n_triangles, counts[0]);
@@ -236,13 +139,6 @@ __global__ void k_boxes(MeshGpuIn in, float reach, float* __restrict__ boxes, fl
 }
 
 // -------------------------------------------------------------- 3 morton ---
-__device__ __forceinline__ uint32_t expand_bits(uint32_t v) {
-  v = (v * 0x00010001u) & 0xFF0000FFu;
-  v = (v * 0x00000101u) & 0x0F00F00Fu;
-  v = (v * 0x00000011u) & 0xC30C30C3u;
-  v = (v * 0x00000005u) & 0x49249249u;
-  return v;
-}
 __global__ void k_morton(const float* __restrict__ cen, const float* __restrict__ pads,
                          const MeshGpuInfo* __restrict__ info, int n, uint32_t* __restrict__ code,
                          uint32_t* __restrict__ idx) {
@@ -250,7 +146,7 @@ __global__ void k_morton(const float* __restrict__ cen, const float* __restrict_
   if (q >= n) return;
   uint32_t cell[3];
   for (int k = 0; k < 3; k++) {
-    const float lo = key_float(info->clo[k]), ext = key_float(info->chi[k]) - lo;
+    const float lo = mesh_key_float(info->clo[k]), ext = mesh_key_float(info->chi[k]) - lo;
     const float inv = ext > 0.f ? 1.f / ext : 0.f;  // an axis of zero extent contributes 0
     cell[k] = (uint32_t)fminf(fmaxf((cen[3 * (int64_t)q + k] - lo) * inv * 1024.0f, 0.0f), 1023.0f);
   }
@@ -260,48 +156,19 @@ __global__ void k_morton(const float* __restrict__ cen, const float* __restrict_
 }
 
 // -------------------------------------------------------------- 5 karras ---
-// common-prefix length of sorted keys i and j (-1 outside); equal keys compare
-// their positions, so every key is distinct (rtp_bvh_gpu.hip delta)
-__device__ __forceinline__ int delta(const uint32_t* __restrict__ code, int n, int i, int j) {
-  if (j < 0 || j >= n) return -1;
-  const uint32_t a = code[i], b = code[j];
-  if (a != b) return __clz(a ^ b);
-  return 32 + __clz((uint32_t)i ^ (uint32_t)j);
-}
-
 // Node ids: internal nodes 0..n-2 (root 0), the radix tree's leaf j (sorted
-// position) = n-1+j.  range: the node's first and last sorted position.
+// position) = n-1+j.  range: the node's first and last sorted position.  Key
+// bit 30 (bounded | unbounded) splits by position like equal keys: axis x.
 __global__ void k_karras(const uint32_t* __restrict__ code, int n, int2* __restrict__ child, int* __restrict__ parent,
                          int8_t* __restrict__ axis, int2* __restrict__ range) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n - 1) return;
-  const int d = (delta(code, n, i, i + 1) - delta(code, n, i, i - 1)) >= 0 ? 1 : -1;
-  const int dmin = delta(code, n, i, i - d);
-  int lmax = 2;
-  while (delta(code, n, i, i + lmax * d) > dmin) lmax <<= 1;
-  int l = 0;
-  for (int t = lmax >> 1; t >= 1; t >>= 1)
-    if (delta(code, n, i, i + (l + t) * d) > dmin) l += t;
-  const int j = i + l * d;
-  const int dnode = delta(code, n, i, j);
-  int s = 0;
-  for (int div = 2;; div <<= 1) {
-    const int t = (l + div - 1) / div;
-    if (delta(code, n, i, i + (s + t) * d) > dnode) s += t;
-    if (t == 1) break;
-  }
-  const int gamma = i + s * d + min(d, 0);
-  const int first = min(i, j), last = max(i, j);
-  const int left = (first == gamma) ? (n - 1 + gamma) : gamma;
-  const int right = (last == gamma + 1) ? (n - 1 + gamma + 1) : gamma + 1;
-  child[i] = make_int2(left, right);
-  range[i] = make_int2(first, last);
-  parent[left] = i;
-  parent[right] = i;
-  // split axis: the Morton bit the range splits on (x at bits 3k+2, y 3k+1,
-  // z 3k); bit 30 (bounded | unbounded) and equal keys split by position: x
-  const int bit = 31 - dnode;
-  axis[i] = (int8_t)((dnode >= 32 || bit == 30) ? 0 : (bit % 3 == 2 ? 0 : (bit % 3 == 1 ? 1 : 2)));
+  const KarrasNode k = karras_node(code, n, i);
+  child[i] = make_int2(k.left, k.right);
+  range[i] = make_int2(k.first, k.last);
+  parent[k.left] = i;
+  parent[k.right] = i;
+  axis[i] = (int8_t)k.axis;
   if (i == 0) parent[0] = -1;
 }
 
@@ -372,42 +239,17 @@ __global__ void k_round(int r, int n, const int2* __restrict__ child, float4* __
 }
 
 // ------------------------------------------------------------- 8 flatten ---
-// f32 -> f16 bits rounded outward (half_outward's rule, rtp_bvh_gpu.hip): the
-// nearest half, stepped outward until its value is on the right side of x
-__device__ uint32_t half_outward(float x, bool up) {
-  uint32_t b = __builtin_bit_cast(uint16_t, (_Float16)x);
-  for (int i = 0; i < 4; i++) {
-    const float v = (float)__builtin_bit_cast(_Float16, (uint16_t)b);
-    if (up ? v >= x : v <= x) return b;
-    const bool neg = (b & 0x8000u) != 0, zero = (b & 0x7fffu) == 0;
-    if (zero) b = up ? 0x0001u : 0x8001u;
-    else if (up) b = neg ? b - 1 : b + 1;
-    else b = neg ? b + 1 : b - 1;
-  }
-  return up ? 0x7c00u : 0xfc00u;
-}
-
 // one thread per emitted node: its depth-first position in each of the 8
-// octant orders (near child first on the parent's split axis) by one climb to
-// the root, then the compact node into each copy
+// octant orders (rtp_lbvh.hpp octant_positions), then the compact node
+// (rtp_mesh_cell.hpp half_outward) into each copy
 __global__ void k_flatten(int n, int n_nodes, const int2* __restrict__ child, const int* __restrict__ parent,
                           const int8_t* __restrict__ axis, const float4* __restrict__ blo,
                           const float4* __restrict__ bhi, const int* __restrict__ size, const int* __restrict__ level,
                           const uint32_t* __restrict__ word, uint4* __restrict__ out) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
   if (x >= 2 * n - 1 || level[x] < 0) return;
-  int pos[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int c = x, p = parent[x]; p >= 0; c = p, p = parent[p]) {
-    const int2 ch = child[p];
-    const int ax = axis[p];
-    const int sl = size[ch.x], sr = size[ch.y];
-#pragma unroll
-    for (int oct = 0; oct < 8; oct++) {
-      const bool neg = (oct >> ax) & 1;  // moving toward lower coordinates: right (upper) child first
-      const int near = neg ? ch.y : ch.x;
-      pos[oct] += (c == near) ? 1 : 1 + (neg ? sr : sl);
-    }
-  }
+  int pos[8];
+  octant_positions(x, 0, child, parent, axis, size, pos);
   const float4 l = blo[x], h = bhi[x];
   uint4 w;
   w.x = half_outward(l.x, false) | half_outward(l.y, false) << 16;
@@ -430,8 +272,8 @@ static_assert(offsetof(DevQuad, e01) == 24 && offsetof(DevQuad, key_lo) == 48 &&
                   offsetof(DevQuad, n) == 88 && offsetof(DevQuad, alb) == 100 && offsetof(DevQuad, mt) == 112,
               "k_quads writes a DevQuad as eight float4s");
 
-// fill_quad (rtp_host.cpp) and rtp_set_scene_mesh's record of stored quad j,
-// the caller's quad idx[j]
+// mesh_records' (rtp_mesh_host.cpp) record of stored quad j, the caller's quad
+// idx[j]: mesh_cell_record's values as eight 16-byte stores
 __global__ void k_quads(MeshGpuIn in, const uint32_t* __restrict__ idx, float4* __restrict__ quads,
                         float4* __restrict__ shade) {
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -440,22 +282,8 @@ __global__ void k_quads(MeshGpuIn in, const uint32_t* __restrict__ idx, float4* 
   const int32_t* id = in.quad_points + 4 * (int64_t)qi;
   const f3 q = load_point(in.points, id[0]), r = load_point(in.points, id[1]), s = load_point(in.points, id[2]),
            t = load_point(in.points, id[3]);
-  const f3 e01 = sub(r, q), e03 = sub(t, q), e21 = sub(r, s), e23 = sub(t, s);
-  const f3 c = cross(sub(r, q), sub(s, q));
-  const float inv = 1.f / sqrtf(dot(c, c));  // vtkm::Normalize: a * (1 / sqrt(dot)), both correctly rounded
-  const f3 nrm = {c.x * inv, c.y * inv, c.z * inv};
-  auto mask_of = [](f3 e) { return (e.x != 0.0f ? 1 : 0) | (e.y != 0.0f ? 2 : 0) | (e.z != 0.0f ? 4 : 0); };
-  const int m01 = mask_of(e01), m03 = mask_of(e03), m21 = mask_of(e21), m23 = mask_of(e23);
-  const int32_t para = (-e01.x == e23.x && -e03.x == e21.x && -e01.y == e23.y && -e03.y == e21.y && -e01.z == e23.z &&
-                        -e03.z == e21.z)
-                           ? 1
-                           : 0;
-  int32_t kind = 0;
-#pragma unroll
-  for (int k = 1; k < kQuadKinds; k++)
-    if (kQuadKind[k].m01 == m01 && kQuadKind[k].m03 == m03 && kQuadKind[k].m21 == m21 && kQuadKind[k].m23 == m23)
-      kind = k;
-  if (mesh_is_triangle(&s.x, &t.x)) kind = kMeshKindTri;  // a triangle cell's mark (rtp_set_scene_mesh's record)
+  const MeshCellRecord c = mesh_cell_record(q, r, s, t, true);
+  const f3 e01 = c.e01, e03 = c.e03, e21 = c.e21, e23 = c.e23, nrm = c.n;
   const int32_t mt = in.mat_chk[in.quad_mat[qi]];
   const float* rgb = in.tex_rgb + 3 * in.tex_chk[in.quad_tex[qi]];
   const float a0 = rgb[0], a1 = rgb[1], a2 = rgb[2];
@@ -463,7 +291,7 @@ __global__ void k_quads(MeshGpuIn in, const uint32_t* __restrict__ idx, float4* 
   Q[0] = f4(q.x, s.x, q.y, s.y);
   Q[1] = f4(q.z, s.z, e01.x, e01.y);
   Q[2] = f4(e01.z, e03.x, e03.y, e03.z);
-  Q[3] = f4(fi(qi), fi(para), fi(qi), fi(kind));  // key_lo = orig = the caller's index
+  Q[3] = f4(fi(qi), fi(c.para), fi(qi), fi(c.kind));  // key_lo = orig = the caller's index
   Q[4] = f4(e21.x, e21.y, e21.z, e23.x);
   Q[5] = f4(e23.y, e23.z, nrm.x, nrm.y);
   Q[6] = f4(nrm.z, a0, a1, a2);
@@ -473,10 +301,6 @@ __global__ void k_quads(MeshGpuIn in, const uint32_t* __restrict__ idx, float4* 
   S[1] = f4(a1, a2, fi(mt), 0.f);
 }
 
-template <typename T>
-hipError_t dalloc(T** p, size_t count) {
-  return hipMalloc(reinterpret_cast<void**>(p), (count ? count : 1) * sizeof(T));
-}
 unsigned blocks(int64_t work) { return (unsigned)((work + kTb - 1) / kTb); }
 
 }  // namespace

@@ -34,7 +34,7 @@ enum MeshGpuFail : uint32_t { kMeshFailPoint = 0, kMeshFailMaterial = 1, kMeshFa
 constexpr uint32_t kMeshNoFail = 0xffffffffu;
 
 // The record the device leaves for the host.  Floats are kept as ordered
-// unsigned keys (mesh_key_float decodes) so that atomic min / max apply.
+// unsigned keys (rtp_mesh_cell.hpp mesh_key_float decodes) so that atomic min / max apply.
 struct MeshGpuInfo {
   uint32_t first_fail;  // min over the failing quads of (q << 2 | MeshGpuFail); kMeshNoFail: none
   uint32_t lo[3], hi[3];    // min / max over all quad vertices
@@ -44,13 +44,6 @@ struct MeshGpuInfo {
   uint32_t pad[1];
 };
 static_assert(sizeof(MeshGpuInfo) == 64, "one small record");
-
-inline float mesh_key_float(uint32_t k) {
-  const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  float f;
-  __builtin_memcpy(&f, &b, 4);
-  return f;
-}
 
 // what the build leaves: the three arrays of DevScene::mesh_* and, for
 // rtp_debug_mesh_readback, each quad's padded box and pad (caller's order)

@@ -1,9 +1,10 @@
 // rtp_mesh_host.cpp -- the host builder of a mesh scene's quad BVH
-// (rtp_set_scene_mesh): descriptor checks, each quad's padded box
-// (rtp_layout.hpp kMeshCosMin has the derivation), the binned-SAH tree and its
-// eight threaded octant copies (rtp_bvh_host.hpp, shared with the sphere BVH),
-// and the walk's compact nodes.  No HIP call: tests and stand-alone programs
-// run it without a device (rtp_mesh_build_host).
+// (rtp_set_scene_mesh): descriptor checks, the scene's bounds, each quad's
+// padded box and record (rtp_mesh_cell.hpp: the functions the device builder
+// calls too), the binned-SAH tree and its eight threaded octant copies
+// (rtp_bvh_host.hpp, shared with the sphere BVH), and the walk's compact
+// nodes.  No HIP call: tests and stand-alone programs run it without a device
+// (rtp_mesh_build_host).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -18,87 +19,6 @@ namespace rtp_host {
 
 namespace {
 rtp_status bad(const char* msg) { return rtp_internal_fail(RTP_ERR_INVALID_ARGUMENT, msg); }
-
-struct d3 {
-  double x, y, z;
-};
-d3 operator-(d3 a, d3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-double dotd(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-d3 crossd(d3 a, d3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-double len(d3 a) { return std::sqrt(dotd(a, a)); }
-d3 ldd(const float* p) { return {p[0], p[1], p[2]}; }
-
-// The pad of one quad (v00 = q, v10 = r, v11 = s, v01 = t), in double:
-// (kMeshRound reach / sine + h) / kMeshCosMin + the slab terms, or kMeshHuge
-// for a strongly non-planar or degenerate quad (rtp_layout.hpp).
-float quad_pad(d3 q, d3 r, d3 s, d3 t, double reach, double amax) {
-  const d3 e01 = r - q, e03 = t - q, e21 = r - s, e23 = t - s;
-  const d3 n1 = crossd(e01, e03);
-  const double A1 = len(n1), A2 = len(crossd(e21, e23));
-  const double l1 = len(e01) * len(e03), l2 = len(e21) * len(e23);
-  if (!(A1 > 0) || !(A2 > 0) || !std::isfinite(A1) || !std::isfinite(A2)) return rtp::kMeshHuge;
-  const double sine = std::min(A1 / l1, A2 / l2);
-  if (!(sine >= rtp::kMeshMinSine)) return rtp::kMeshHuge;
-  const double h = std::fabs(dotd(s - q, n1)) / A1;  // v11 off the first triangle's plane
-  if (h > 0) {
-    // the fold: v11's projection lies w beyond the diagonal (v10, v01), away from v00
-    const d3 diag = t - r;
-    d3 u1 = crossd(n1, diag);
-    const double lu = len(u1);
-    if (!(lu > 0)) return rtp::kMeshHuge;
-    const double side = dotd(q - r, u1) < 0 ? 1.0 : -1.0;  // u1 points away from v00
-    const double w = side * dotd(s - r, u1) / lu;
-    if (!(w > 0) || !(h / w < 0.5 * rtp::kMeshCosMin)) return rtp::kMeshHuge;
-  }
-  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
-  const double pad = ((double)rtp::kMeshRound * reach / sine + h) / (double)rtp::kMeshCosMin + slab;
-  if (!(pad < reach)) return rtp::kMeshHuge;
-  return std::nextafter((float)pad, INFINITY);
-}
-
-// The pad of a triangle cell (v11 == v01: the reference's test accepts only
-// its first triangle v00 = q, v10 = r, v01 = t): the roundings and the slab
-// terms of quad_pad over the sine of the corner at v00 alone, no h and no fold
-// (rtp_layout.hpp kMeshCosMin, "Triangle cells").
-float tri_pad(d3 q, d3 r, d3 t, double reach, double amax) {
-  const d3 e01 = r - q, e03 = t - q;
-  const double A1 = len(crossd(e01, e03));
-  const double l1 = len(e01) * len(e03);
-  if (!(A1 > 0) || !std::isfinite(A1)) return rtp::kMeshHuge;
-  const double sine = A1 / l1;
-  if (!(sine >= rtp::kMeshMinSine)) return rtp::kMeshHuge;
-  const double slab = 1e-5 + 0x1p-16 * amax + 0x1p-18 * reach;
-  const double pad = ((double)rtp::kMeshRound * reach / sine) / (double)rtp::kMeshCosMin + slab;
-  if (!(pad < reach)) return rtp::kMeshHuge;
-  return std::nextafter((float)pad, INFINITY);
-}
-
-// the ordered key of a half: key k >= 0 is the half with bits k, k < 0 its negative
-float half_value(int key) {
-  const int b = key < 0 ? -key : key;
-  const int e = b >> 10, m = b & 0x3ff;
-  const float v = e == 0 ? std::ldexp((float)m, -24) : e == 31 ? INFINITY : std::ldexp((float)(m | 0x400), e - 25);
-  return key < 0 ? -v : v;
-}
-// f32 -> f16 bits rounded outward: the smallest half >= x (up) or the largest <= x
-uint32_t half_outward(float x, bool up) {
-  if (std::isnan(x)) return up ? 0x7c00u : 0xfc00u;
-  int lo = -0x7c00, hi = 0x7c00;  // -inf .. +inf
-  if (up) {
-    while (lo < hi) {
-      const int mid = lo + (hi - lo) / 2;
-      if (half_value(mid) >= x) hi = mid;
-      else lo = mid + 1;
-    }
-  } else {
-    while (lo < hi) {
-      const int mid = lo + (hi - lo + 1) / 2;
-      if (half_value(mid) <= x) lo = mid;
-      else hi = mid - 1;
-    }
-  }
-  return lo < 0 ? 0x8000u | (uint32_t)(-lo) : (uint32_t)lo;
-}
 }  // namespace
 
 rtp_status mesh_validate_head(const rtp_scene_desc* s) {
@@ -146,60 +66,47 @@ rtp_status mesh_validate(const rtp_scene_desc* s) {
   return mesh_validate_tail(s);
 }
 
-rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
-  const rtp_status rs = mesh_validate(s);
-  if (rs != RTP_OK) return rs;
-  const int n = s->n_quads;
-  // the reach: kBvhReachFactor diagonals of the scene's bounding box (every
-  // quad vertex, every sphere's c -+ r), as for the sphere BVH
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int q = 0; q < n; q++)
+void scene_bounds(const rtp_scene_desc* s, bool quads, float lo_io[3], float hi_io[3]) {
+  float lo[3], hi[3];  // (locals: the caller's arrays could alias the points)
+  for (int k = 0; k < 3; k++) lo[k] = lo_io[k], hi[k] = hi_io[k];
+  for (int q = 0; q < (quads ? s->n_quads : 0); q++)
     for (int c = 0; c < 4; c++)
       for (int k = 0; k < 3; k++) {
         const float v = s->points[3 * s->quad_points[4 * q + c] + k];
-        lo[k] = std::min(lo[k], v), hi[k] = std::max(hi[k], v);
+        lo[k] = rtp::min_of(lo[k], v), hi[k] = rtp::max_of(hi[k], v);
       }
   for (int j = 0; j < s->n_spheres; j++)
     for (int k = 0; k < 3; k++) {
       const float c = s->points[3 * s->sphere_point[j] + k], r = s->sphere_radius[j];
-      lo[k] = std::min(lo[k], c - r), hi[k] = std::max(hi[k], c + r);
+      lo[k] = rtp::min_of(lo[k], c - r), hi[k] = rtp::max_of(hi[k], c + r);
     }
-  const float ex = hi[0] - lo[0], ey = hi[1] - lo[1], ez = hi[2] - lo[2];
-  B.reach = rtp::kBvhReachFactor * std::sqrt(ex * ex + ey * ey + ez * ez);
-  if (!std::isfinite(B.reach)) return mesh_bounds_fail();
+  for (int k = 0; k < 3; k++) lo_io[k] = lo[k], hi_io[k] = hi[k];
+}
+
+rtp_status mesh_build(const rtp_scene_desc* s, MeshBuild& B, int leaf_size) {
+  const rtp_status rs = mesh_validate(s);
+  if (rs != RTP_OK) return rs;
+  const int n = s->n_quads;
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  scene_bounds(s, true, lo, hi);
+  B.reach = rtp::scene_reach(lo, hi);
+  if (!rtp::finite_f(B.reach)) return mesh_bounds_fail();
   B.boxes.resize((size_t)6 * n);
   B.pads.resize(n);
   B.n_triangles = B.n_unbounded = 0;
   std::vector<BvhPrim> P(n);
   for (int q = 0; q < n; q++) {
-    const float* v[4];
-    for (int c = 0; c < 4; c++) v[c] = s->points + 3 * s->quad_points[4 * q + c];
-    // a triangle cell: v11 and v01 compare equal (include/rtp_mesh.h)
-    const bool tri = rtp::mesh_is_triangle(v[2], v[3]);
-    float mn[3], mx[3];
+    const int32_t* id = s->quad_points + 4 * q;
+    const rtp::MeshCellBox c = rtp::mesh_cell_box(rtp::load_f3(s->points + 3 * id[0]), rtp::load_f3(s->points + 3 * id[1]),
+                                                  rtp::load_f3(s->points + 3 * id[2]), rtp::load_f3(s->points + 3 * id[3]),
+                                                  B.reach);
+    B.pads[q] = c.pad;
+    B.n_triangles += c.tri ? 1 : 0;
+    B.n_unbounded += c.pad == rtp::kMeshHuge ? 1 : 0;
     for (int k = 0; k < 3; k++) {
-      if (tri) {  // the accepted region is the triangle: its three vertices
-        mn[k] = std::min(std::min(v[0][k], v[1][k]), v[3][k]);
-        mx[k] = std::max(std::max(v[0][k], v[1][k]), v[3][k]);
-        continue;
-      }
-      // the four vertices and v00 + e01 + e03 with the device's float edges
-      const float far = v[0][k] + (v[1][k] - v[0][k]) + (v[3][k] - v[0][k]);
-      mn[k] = std::min(std::min(std::min(v[0][k], v[1][k]), std::min(v[2][k], v[3][k])), far);
-      mx[k] = std::max(std::max(std::max(v[0][k], v[1][k]), std::max(v[2][k], v[3][k])), far);
-    }
-    double amax = 0;
-    for (int k = 0; k < 3; k++) amax = std::max(amax, (double)std::max(std::fabs(mn[k]), std::fabs(mx[k])));
-    const float pad = tri ? tri_pad(ldd(v[0]), ldd(v[1]), ldd(v[3]), B.reach, amax)
-                          : quad_pad(ldd(v[0]), ldd(v[1]), ldd(v[2]), ldd(v[3]), B.reach, amax);
-    B.pads[q] = pad;
-    B.n_triangles += tri ? 1 : 0;
-    B.n_unbounded += pad == rtp::kMeshHuge ? 1 : 0;
-    for (int k = 0; k < 3; k++) {
-      // (one step outward: the float sums may round toward the quad)
-      P[q].lo[k] = B.boxes[6 * (size_t)q + k] = std::nextafter(mn[k] - pad, -INFINITY);
-      P[q].hi[k] = B.boxes[6 * (size_t)q + 3 + k] = std::nextafter(mx[k] + pad, INFINITY);
-      P[q].cen[k] = 0.5f * mn[k] + 0.5f * mx[k];
+      P[q].lo[k] = B.boxes[6 * (size_t)q + k] = c.lo[k];
+      P[q].hi[k] = B.boxes[6 * (size_t)q + 3 + k] = c.hi[k];
+      P[q].cen[k] = c.cen[k];
     }
     P[q].idx = q;
   }
@@ -241,10 +148,45 @@ void mesh_compact(const rtp::BvhNode* nodes, int64_t total, uint32_t* out) {
   for (int64_t i = 0; i < total; i++) {
     const rtp::BvhNode& nd = nodes[i];
     uint32_t* w = out + 4 * i;
-    w[0] = half_outward(nd.lo[0], false) | half_outward(nd.lo[1], false) << 16;
-    w[1] = half_outward(nd.lo[2], false) | half_outward(nd.hi[0], true) << 16;
-    w[2] = half_outward(nd.hi[1], true) | half_outward(nd.hi[2], true) << 16;
+    w[0] = rtp::half_outward(nd.lo[0], false) | rtp::half_outward(nd.lo[1], false) << 16;
+    w[1] = rtp::half_outward(nd.lo[2], false) | rtp::half_outward(nd.hi[0], true) << 16;
+    w[2] = rtp::half_outward(nd.hi[1], true) | rtp::half_outward(nd.hi[2], true) << 16;
     w[3] = nd.leaf == 0 ? (uint32_t)nd.skip : rtp::kCBvhLeafBit | (uint32_t)nd.leaf;
+  }
+}
+
+void fill_quad(rtp::DevQuad& Q, const float* q, const float* r, const float* s, const float* t, bool mesh) {
+  const rtp::MeshCellRecord c =
+      rtp::mesh_cell_record(rtp::load_f3(q), rtp::load_f3(r), rtp::load_f3(s), rtp::load_f3(t), mesh);
+  std::memset(&Q, 0, sizeof(Q));
+  for (int k = 0; k < 3; k++) {
+    Q.vv[k][0] = q[k], Q.vv[k][1] = s[k];
+    Q.e01[k] = (&c.e01.x)[k], Q.e03[k] = (&c.e03.x)[k];
+    Q.e21[k] = (&c.e21.x)[k], Q.e23[k] = (&c.e23.x)[k];
+    Q.n[k] = (&c.n.x)[k];
+  }
+  Q.para = c.para;
+  Q.kind = c.kind;
+}
+
+void mesh_records(const rtp_scene_desc* s, const MeshBuild& build, std::vector<rtp::DevQuad>& quads,
+                  std::vector<float>& shade) {
+  const int n = s->n_quads;
+  quads.resize(n);
+  shade.assign((size_t)8 * n, 0.f);
+  for (int j = 0; j < n; j++) {
+    const int q = build.order[j];
+    const int32_t* id = s->quad_points + 4 * q;
+    rtp::DevQuad& Q = quads[j];
+    fill_quad(Q, s->points + 3 * id[0], s->points + 3 * id[1], s->points + 3 * id[2], s->points + 3 * id[3], true);
+    Q.mt = s->mat_type[s->quad_mat[q]];
+    std::memcpy(Q.alb, s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]], 12);
+    Q.orig = q;
+    Q.key_lo = (uint32_t)q;  // the caller's index: the hit's index and the tie-break of equal t
+    float* sh = shade.data() + (size_t)8 * q;
+    std::memcpy(sh, Q.n, 12);
+    std::memcpy(sh + 3, Q.alb, 12);
+    std::memcpy(sh + 6, &Q.mt, 4);
   }
 }
 

@@ -5,7 +5,7 @@ small variants of it that sit on each side of the host's scene-setup gates
 duplicates).  Plain numpy and ctypes over oracle_ctypes.Scene: no GPU.
 
 classify() restates the classification from its definition (rtp_layout.hpp
-kQuadKind, rtp_host.cpp fill_quad); nothing here is imported from the library,
+kQuadKind, rtp_mesh_cell.hpp mesh_cell_record); nothing here is imported from the library,
 so the tests can hold the library's own tally against it."""
 from __future__ import annotations
 

@@ -8,7 +8,7 @@ imported: the float32 sphere root (rtp_kernels.hip sphere_root, the oracle's
 sphere_hit), the pad of a sphere's box (rtp_host.cpp rtp_set_scene,
 rtp_bvh_gpu.hip k_boxes; the pad before the soundness bound is kept as
 pad_old for the guard that shows what that bound is for) and the outward
-rounding to half precision (rtp_bvh_gpu.hip half_outward).
+rounding to half precision (rtp_mesh_cell.hpp half_outward).
 
 Walk orders.  Both builders keep spheres with equal keys in index order (the
 host's stable partition and its sort by index, the device's stable radix sort
@@ -282,6 +282,16 @@ def concentric():
     return _done(z)
 
 
+def concentric9():
+    """9 spheres (the smallest set behind the BVH) about one centre, radii
+    increasing with the index: every Morton code is equal, so the device
+    builder's radix tree splits by position alone."""
+    z = room()
+    for k, r in enumerate(np.linspace(0.05, 0.33, 9)):
+        z.add_sphere((0.5, 0.45, 0.5), r, GLASS if k % 2 else LAMBERT[k % 3])
+    return _done(z)
+
+
 def near_ties():
     """32 pairs (k, k + 32) of equal-radius spheres whose centres differ by
     1e-5..1e-4 along one axis (z, toward the camera, for two pairs in three);
@@ -382,6 +392,7 @@ VARIANTS = {
     "duplicates": duplicates,
     "all_equal": all_equal,
     "concentric": concentric,
+    "concentric9": concentric9,
     "near_ties": near_ties,
     "line": line,
     "plane": plane,

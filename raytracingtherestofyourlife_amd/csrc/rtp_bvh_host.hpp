@@ -1,5 +1,5 @@
 // rtp_bvh_host.hpp -- the host BVH builder shared by the sphere BVH
-// (rtp_host.cpp) and the mesh BVH (rtp_mesh_host.cpp): binned SAH over
+// (rtp_scene_host.cpp) and the mesh BVH (rtp_mesh_host.cpp): binned SAH over
 // primitives given as boxes with a centroid.  Host only, no HIP call.
 #pragma once
 #include <algorithm>

@@ -1,5 +1,7 @@
 // rtp_context.hpp -- the rtp_context behind the C ABI (include/rtp.h),
-// shared by rtp_host.cpp (path mode) and rtp_direct_host.cpp (-direct mode).
+// shared by the host units that touch a device: rtp_host.cpp (path mode),
+// rtp_debug_host.cpp, rtp_direct_host.cpp (-direct mode), rtp_adaptive_host.cpp
+// and the host half of rtp_denoise.hip.  (rtp_internal_fail: rtp_host_base.hpp)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -90,5 +92,3 @@ struct rtp_context {
   size_t adapt_state_bytes = 0;
   double adapt_ms[4] = {0, 0, 0, 0};
 };
-// thread-local last-error message of the C ABI (rtp_host.cpp)
-rtp_status rtp_internal_fail(rtp_status st, const std::string& msg);

@@ -1,32 +1,30 @@
-// rtp_host.cpp -- host side of librtp.so: the C ABI declared in include/rtp.h.
+// rtp_host.cpp -- host side of librtp.so: the contexts of the C ABI declared
+// in include/rtp.h, their scenes and their renders.
 //
 // Mirrors vtkm::rendering::MapperPathTracer (MapperPathTracer.cxx:94-538):
-// the scene/material tables, the camera set-up of pathtracing::Camera
-// (Camera.cxx:437-474, 624-776, 879-960) and the render entry point.  All
-// ray-independent quantities are precomputed here with the reference's own
-// float operations (compiled with -ffp-contract=off; x86-64 SSE2 arithmetic
-// is IEEE single/double, the same as the reference's g++ build).
+// a context's life cycle, the upload of a built scene (the build itself:
+// rtp_scene_host.cpp, rtp_mesh_host.cpp) and the render entry points with the
+// camera set-up of pathtracing::Camera (Camera.cxx:437-474, 624-776, 879-960;
+// rtp_host_base.hpp camera_setup).  The RNG jump tables are rtp_ff_host.cpp's,
+// the diagnostics and test hooks rtp_debug_host.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <cstdio>
 #include <cstring>
-#include <memory>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/rtp.h"
 #include "../../include/rtp_mesh.h"
 #include "rtp_context.hpp"
-#include "rtp_bvh_host.hpp"
+#include "rtp_ff.hpp"
 #include "rtp_host_util.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_mesh.hpp"
 #include "rtp_mesh_gpu.hpp"
+#include "rtp_scene.hpp"
 
 extern "C" const char* rtp_instance_name(int variant, int stats, int walk, int tiles, int plan, int steal, int views,
                                          int resume);
@@ -35,385 +33,14 @@ extern "C" int rtp_plan_steal(int64_t npix, int bvh);
 extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves, int bvh,
                                         int stats, int steal, hipStream_t stream, int lds_bytes);
 extern "C" int rtp_lds_walk_capacity(void);
-extern "C" hipError_t rtp_launch_eval_primitive(int kind, const void* in, void* out, int64_t n, const uint32_t* tab,
-                                                uint32_t t1, uint32_t t2, hipStream_t stream);
-extern "C" hipError_t rtp_launch_build_ff_tables(const rtp::FfBuildOut* out, int max_r, uint32_t t1, uint32_t t2,
-                                                 hipStream_t stream);
 extern "C" hipError_t rtp_compact_bvh(const rtp::BvhNode* d_nodes, int64_t total, uint32_t* d_cn, int32_t* d_cidx,
                                       hipStream_t stream);
 extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, float reach,
                                         rtp::BvhNode* d_nodes, rtp::DevSphereG* d_geom, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const float* rays, uint32_t* out,
-                                              int64_t n, int bvh, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const float* rays, const uint32_t* seeds,
-                                             uint32_t* out, int64_t n, int bvh, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_raygen(const rtp::DevCamera* cam, int nx, int ny, const int64_t* pixels,
-                                             const uint32_t* seeds, uint32_t* out, int64_t n, hipStream_t stream);
 extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
                                         hipStream_t stream);
-extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
-                                                  uint32_t* first_bad, hipStream_t stream);
 
 using namespace rtp_host;
-
-namespace {
-
-thread_local std::string g_err;
-
-// which = min(3, int(r*3+1)), r = float(t)/4294967295.f  (PdfWorklet.h:20)
-int which_of_hash(uint32_t t) {
-  float r = (float)t / 4294967295.f;
-  int w = (int)(r * 3 + 1);
-  return w < 3 ? w : 3;
-}
-// smallest hash value with which >= w (which is monotone in t)
-uint32_t which_threshold(int w) {
-  uint64_t lo = 0, hi = 0x100000000ull;  // answer in [lo, hi]
-  while (lo < hi) {
-    uint64_t mid = (lo + hi) / 2;
-    if (which_of_hash((uint32_t)mid) >= w)
-      hi = mid;
-    else
-      lo = mid + 1;
-  }
-  return lo > 0xffffffffull ? 0xffffffffu : (uint32_t)lo;
-}
-
-bool bit_equal(const float* a, const float* b, int n) { return std::memcmp(a, b, sizeof(float) * n) == 0; }
-
-// Closest-hit prefilter tables (rtp_kernels.hip closest_hit):
-// the quads of groups 0..5 (kinds 1..6, edges along two axes) lie in a plane
-// x[axis] = const, bit for bit.  Each gets that plane and a box around its
-// vertices in the other two coordinates, widened outward by a few ulps so
-// that the float box contains the real one.  Enabled only when every such
-// quad qualifies, they fit kMaxPre, and the scene is within the coordinate
-// range the kernel's error margins assume (|x| <= kPreLim).
-constexpr float kPreLim = 16.0f;
-void setup_prefilter(rtp::DevScene* h, const rtp_scene_desc* s, const std::vector<int>& kept) {
-  h->n_pre = 0;
-  for (int a = 0; a <= 3; a++) h->pre_begin[a] = 0;
-  h->pre_scale = 0.0f;
-  const int n = h->kind_begin[6];
-  if (n <= 0 || n > rtp::kMaxPre) return;
-  if (env_is("RTP_PREFILTER", '0')) return;
-  std::vector<int> axis_of(n);
-  std::vector<rtp::PreQuad> pq(n);
-  float scale = 0.0f;
-  for (int q = 0; q < n; q++) {
-    const rtp::DevQuad& Q = h->quads[q];
-    const rtp::QuadKindMasks& K = rtp::kQuadKind[Q.kind];
-    const int flat = 7 & ~(K.m01 | K.m03);
-    if (Q.kind < 1 || Q.kind > 6 || (flat != 1 && flat != 2 && flat != 4)) return;
-    const int a = flat == 1 ? 0 : flat == 2 ? 1 : 2, b = (a + 1) % 3, c = (a + 2) % 3;
-    if (!Q.para) return;  // (unreachable: kinds 1..6 are exact parallelograms, see mesh_cell_record)
-    {
-      const int ei = K.m01 == 1 ? 0 : K.m01 == 2 ? 1 : 2, ej = K.m03 == 1 ? 0 : K.m03 == 2 ? 1 : 2;
-      const int ea = 3 - ei - ej;
-      rtp::PreExact& E = h->prex[q];
-      std::memset(&E, 0, sizeof(E));
-      E.i = ei;
-      E.s = (ej == (ei + 1) % 3) ? 1 : -1;
-      E.b = Q.e01[ei], E.c = Q.e03[ej];
-      E.bs = E.s > 0 ? E.b : -E.b, E.cs = E.s > 0 ? E.c : -E.c;
-      E.vi = Q.vv[ei][0], E.va = Q.vv[ea][0], E.vj = Q.vv[ej][0];
-      E.wi = Q.vv[ei][1], E.wa = Q.vv[ea][1], E.wj = Q.vv[ej][1];
-      E.key_lo = Q.key_lo;
-    }
-    const int32_t* id = s->quad_points + 4 * kept[Q.orig];
-    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    const float x = s->points[3 * id[0] + a];
-    for (int k = 0; k < 4; k++) {
-      const float* v = s->points + 3 * id[k];
-      if (!(v[a] == x)) return;  // not in one axis plane
-      for (int j = 0; j < 3; j++) {
-        if (!std::isfinite(v[j])) return;
-        lo[j] = std::min(lo[j], (double)v[j]);
-        hi[j] = std::max(hi[j], (double)v[j]);
-        scale = std::max(scale, std::fabs(v[j]));
-      }
-    }
-    auto centre_half = [&](int j, float& cen, float& half) {
-      cen = (float)(0.5 * (lo[j] + hi[j]));
-      const double need = std::max(hi[j] - (double)cen, (double)cen - lo[j]);
-      half = (float)need;
-      for (int u = 0; u < 2; u++) half = std::nextafter(half, INFINITY);  // >= need after rounding
-    };
-    rtp::PreQuad& P = pq[q];
-    std::memset(&P, 0, sizeof(P));
-    P.x = x;
-    centre_half(b, P.cb, P.rb);
-    centre_half(c, P.cc, P.rc);
-    P.qpos = q;
-    axis_of[q] = a;
-  }
-  if (!(scale <= kPreLim)) return;
-  int pos = 0;
-  for (int a = 0; a < 3; a++) {
-    h->pre_begin[a] = pos;
-    for (int q = 0; q < n; q++)
-      if (axis_of[q] == a) h->pre[pos++] = pq[q];
-  }
-  h->pre_begin[3] = pos;
-  h->pre_scale = scale;
-  h->n_pre = n;
-}
-
-// RNG jump tables.  A dead depth consumes 1 + {2,3,2} draws chosen by the
-// `which` draw against two constant thresholds (lightables = 2,
-// MapperPathTracer.cxx:218; PdfWorklet.h:20), so "advance the state over k
-// dead depths" is a fixed map of the 32-bit state.  Chain table j tabulates
-// it for k = 32 >> j over all 2^32 states (16 GiB each), and the direct
-// tables for each k in [d_first, d_first + d_count): a finished sample whose
-// remaining count falls in the direct block is fast-forwarded by ONE gather,
-// others by a chain of gathers plus a few hashed depths (rtp_render_pool).
-// Defaults: 4 chain tables (32, 16, 8, 4) and direct tables 41..50 (the
-// counts a depth-50 render's samples mostly have), 224 GiB in all;
-// RTP_FF_TABLES=n (0..6) / RTP_FF_DIRECT=n / RTP_FF_DIRECT_FIRST=r change
-// the set, and it shrinks to the free device memory (8 GiB kept free).
-// The tables are per device and process, shared by every context, and built
-// by the policy of rtp_set_ff_tables (include/rtp.h): what they cost
-// (allocation + build, measured here) against what they save per sample.
-struct FfTables {
-  uint32_t* t[rtp::kFfTables] = {};
-  uint32_t* direct = nullptr;  // d_count tables of 2^32 entries, contiguous
-  int d_first = 0, d_count = 0, n_chain = 0;
-  int stage = 0;  // built so far: 1 chain tables, 2 + direct tables
-  double alloc_ms = 0, build_ms = 0;
-  double chain_alloc_ms = -1;  // the chain stage's own allocation time (-1: not built)
-  uint64_t chain_at = 0;       // samples_seen when the chain stage was built
-  uint64_t bytes = 0;
-  uint64_t samples_seen = 0;  // samples launched on this device (the AUTO policy's count)
-};
-std::mutex g_ff_mu;
-FfTables g_ff[64];
-
-int ff_policy_default() {
-  const char* e = getenv("RTP_FF_POLICY");
-  if (e && !std::strcmp(e, "on")) return RTP_FF_TABLES_ON;
-  if (e && !std::strcmp(e, "off")) return RTP_FF_TABLES_OFF;
-  return RTP_FF_TABLES_AUTO;
-}
-
-// AUTO builds in two stages, each once the samples launched on the device
-// (this launch included) reach its break-even count: setup time over the
-// kernel time it saves per sample (C2 on MI355X; round 5,
-// profiles/r05z_ff_policy.txt: no tables 126.0 ms, chain tables 106.8 ms,
-// all 98.9 ms per 6.4e8 samples):
-//  - chain tables (64 GiB): 0.12 s build + an allocation that takes 1 ms to
-//    ~1.5 s depending on the box (the driver clearing the memory), saving
-//    3.0e-11 s/sample: 7.5e9 samples, ~12 C2 renders (allows ~0.1 s of
-//    allocation);
-//  - direct tables (+160 GiB): 0.07 s more build + 2.5x the chain stage's
-//    measured allocation time, saving 1.23e-11 s/sample: counted from the
-//    chain stage, ~9 C2 renders where allocation is fast, ~450 where the
-//    chain's 64 GiB took 1.4 s; 3e11 samples before the chain stage is built.
-// RTP_FF_AUTO_SAMPLES=chain[,direct] overrides (absolute counts).
-constexpr double kFfChainSavePerSample = 3.0e-11, kFfDirectSavePerSample = 1.23e-11;
-constexpr double kFfDirectBuildS = 0.07, kFfDirectAllocRatio = 160.0 / 64.0;
-void ff_auto_samples(uint64_t& chain, uint64_t& direct, const FfTables* T = nullptr) {
-  chain = 7500000000ull;
-  direct = 300000000000ull;
-  if (const char* e = getenv("RTP_FF_AUTO_SAMPLES")) {
-    char* end = nullptr;
-    chain = std::strtoull(e, &end, 10);
-    direct = (end && *end == ',') ? std::strtoull(end + 1, nullptr, 10) : chain;
-    return;
-  }
-  if (T && T->chain_alloc_ms >= 0) {
-    const double setup_s = kFfDirectBuildS + kFfDirectAllocRatio * T->chain_alloc_ms / 1e3;
-    direct = std::min<uint64_t>(direct, T->chain_at + (uint64_t)(setup_s / kFfDirectSavePerSample));
-  }
-  (void)kFfChainSavePerSample;
-}
-
-// Allocate and build the tables of a device up to `stage` (caller holds
-// g_ff_mu): 1 the chain tables, 2 also the direct block.  The new tables are
-// allocated and built through local pointers and published into T only once
-// the build kernel has finished: a launch that took its snapshot (FfSnap)
-// earlier, and may still be running on another stream, never sees a table
-// that is half built, and a failed build frees only what it allocated.
-void ff_build(FfTables& T, int stage) {
-  if (T.stage >= stage) return;
-  int want = 4, nd = 10, first = 41;
-  if (const char* env = getenv("RTP_FF_TABLES")) want = std::max(0, std::min(rtp::kFfTables, atoi(env)));
-  if (const char* env = getenv("RTP_FF_DIRECT")) nd = std::max(0, std::min(32, atoi(env)));
-  if (const char* env = getenv("RTP_FF_DIRECT_FIRST")) first = std::max(1, atoi(env));
-  if (first + nd > rtp::kFfMaxSteps) nd = std::max(0, rtp::kFfMaxSteps - first);
-  if (want == 0) nd = 0;  // (RTP_FF_TABLES=0: no tables at all)
-  const size_t bytes = (size_t)4 << 32, reserve = 8ull << 30;
-  auto fits = [&](size_t n) {
-    size_t free_b = 0, total_b = 0;
-    return hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b >= n + reserve;
-  };
-  rtp::FfBuildOut out{};
-  uint32_t* chain[rtp::kFfTables] = {};
-  uint32_t* direct = nullptr;
-  int n_chain = 0, d_count = 0;
-  int max_r = 0;
-  const auto t0 = std::chrono::steady_clock::now();
-  if (T.stage < 1) {
-    for (int j = 0; j < want; j++) {
-      if (!fits(bytes) || hipMalloc(&chain[j], bytes) != hipSuccess) {
-        chain[j] = nullptr;
-        break;
-      }
-      n_chain = j + 1;
-      out.t[32 >> j] = chain[j];
-      max_r = std::max(max_r, 32 >> j);
-    }
-  }
-  if (stage >= 2 && nd > 0) {
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
-      nd = std::min<int>(nd, free_b > reserve ? (int)((free_b - reserve) / bytes) : 0);
-    else
-      nd = 0;
-    if (nd > 0 && hipMalloc(&direct, bytes * (size_t)nd) == hipSuccess) {
-      d_count = nd;
-      for (int k = 0; k < nd; k++) {
-        out.t[first + k] = direct + (size_t)k * (bytes / 4);
-        max_r = std::max(max_r, first + k);
-      }
-    } else {
-      direct = nullptr;
-    }
-  }
-  (void)hipGetLastError();
-  const double alloc_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  T.alloc_ms += alloc_ms;
-  if (T.stage < 1 && stage == 1 && n_chain > 0) {  // the AUTO policy's estimate of the direct stage's cost
-    T.chain_alloc_ms = alloc_ms;
-    T.chain_at = T.samples_seen;
-  }
-  T.stage = stage;  // (a failed stage is not retried)
-  if (max_r > 0) {
-    const uint32_t t1 = which_threshold(2), t2 = which_threshold(3);
-    hipEvent_t a = nullptr, b = nullptr;
-    bool ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-    ok = ok && hipEventRecord(a, nullptr) == hipSuccess;
-    ok = ok && rtp_launch_build_ff_tables(&out, max_r, t1, t2, nullptr) == hipSuccess;
-    ok = ok && hipEventRecord(b, nullptr) == hipSuccess && hipEventSynchronize(b) == hipSuccess;
-    float ms = 0;
-    if (ok) (void)hipEventElapsedTime(&ms, a, b);
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-    (void)hipGetLastError();
-    if (!ok) {  // nothing was published: free this stage's own allocations
-      for (uint32_t* p : chain)
-        if (p) (void)hipFree(p);
-      if (direct) (void)hipFree(direct);
-      return;
-    }
-    T.build_ms += ms;
-  }
-  // publish (the build has completed)
-  for (int j = 0; j < n_chain; j++) T.t[j] = chain[j];
-  if (n_chain > 0) T.n_chain = n_chain;
-  if (d_count > 0) {
-    T.direct = direct;
-    T.d_first = first;
-    T.d_count = d_count;
-  }
-  T.bytes = bytes * (size_t)(T.n_chain + T.d_count);
-}
-
-// What one launch reads of a device's tables: a copy taken under g_ff_mu,
-// so a later stage being built by another thread cannot change it.
-struct FfSnap {
-  const uint32_t* t[rtp::kFfTables] = {};
-  const uint32_t* direct = nullptr;
-  int d_first = 0, d_count = 0;
-};
-
-// The tables a launch of `samples` samples on `device` uses under `policy`
-// (built first when the policy says so).  The tables, once published, stay
-// until the process ends.
-FfSnap ff_tables(int device, int policy, uint64_t samples) {
-  std::lock_guard<std::mutex> lk(g_ff_mu);
-  FfTables& T = g_ff[device & 63];
-  T.samples_seen += samples;
-  if (policy == RTP_FF_TABLES_ON) {
-    ff_build(T, 2);
-  } else if (policy == RTP_FF_TABLES_AUTO) {
-    uint64_t chain = 0, direct = 0;
-    ff_auto_samples(chain, direct, &T);
-    if (T.samples_seen >= direct) ff_build(T, 2);
-    else if (T.samples_seen >= chain) ff_build(T, 1);
-  }
-  FfSnap s;
-  if (policy == RTP_FF_TABLES_OFF) return s;
-  for (int j = 0; j < rtp::kFfTables; j++) s.t[j] = T.t[j];
-  s.direct = T.direct;
-  s.d_first = T.d_first;
-  s.d_count = T.d_count;
-  return s;
-}
-
-// Sphere BVH (replaces the VTK-m LinearBVH of buildBVH, MapperPathTracer.cxx:
-// 437-449, for scenes with many spheres).  Binned SAH (16 bins per axis) with
-// deterministic partitions, leaves of <= kBvhLeafSize spheres.  The tree is
-// flattened eight times, once per ray-direction octant: each copy is a
-// depth-first "threaded" array (hit: next node; miss or leaf done: skip) that
-// visits the child on the near side of the split axis first, so a lane walks
-// near-to-far without a stack and the closest-hit bound culls early.  Boxes
-// only cull: each sphere box is padded (rtp_layout.hpp bvh_sphere_pad, from
-// the roundings of the device's float sphere test) so that every ray that
-// test accepts, and the point it returns, lie inside it, and the kernel
-// compares against a slack-widened [0, t_best] interval.  The
-// closest hit is the lexicographic min of (t, kind, index) whatever the order.
-// (BvhPrim, TNode, bvh_build and the threaded flattening: rtp_bvh_host.hpp, shared with the mesh BVH)
-
-// inner nodes of the sphere BVH above this depth are dropped from the walks'
-// arrays (bvh_flatten below)
-constexpr int kBvhDropDepth = 2;
-constexpr float kBvhDropArea = 0.6f;  // (0: off)
-
-// threaded flattening for one octant (bit k set: direction component k < 0)
-// A one-sphere leaf carries the sphere itself (rtp::kBvhLeafSphere): lo =
-// centre, hi[0] = r*r, hi[1] = the sphere's index (as int bits), so the walk
-// runs the exact root test without a box test or a second dependent load.
-// Inner nodes above depth `drop` are not emitted: their children take their
-// place in the order (the skip of the node before them then lands on their
-// first emitted descendant), so the walk treats their boxes as hit.  A box
-// only culls, so this changes which nodes a ray visits, never its hit.  The
-// top boxes (the whole sphere cloud, its halves) are hit by nearly every ray
-// from inside the room: each one dropped is one dependent gather and box test
-// fewer per walk.
-// Below that, with drop_sa > 0, an inner node with two inner children is
-// dropped too when its surface area exceeds drop_sa of its parent's (a ray
-// that reaches it would hit its box with about that probability: dropping it
-// saves one visit when it would be hit and costs one when it would not).
-void bvh_flatten(const std::vector<TNode>& T, int t, int oct, const std::vector<int32_t>& order,
-                 const std::vector<rtp::DevSphere>& sph, std::vector<rtp::BvhNode>& out, int drop = 0,
-                 float drop_sa = 0.f) {
-  bvh_thread(
-      T, t, oct, out,
-      [&](const TNode& s, rtp::BvhNode& nd) {
-        if (RTP_BVH_EMBED && s.count == 1) {
-          const rtp::DevSphere& S = sph[order[s.first]];
-          std::memcpy(nd.lo, S.c, sizeof(nd.lo));
-          nd.hi[0] = S.rr;
-          int32_t orig = order[s.first];
-          std::memcpy(&nd.hi[1], &orig, sizeof(orig));
-          nd.hi[2] = 0.f;
-          nd.leaf = rtp::kBvhLeafSphere;
-        } else {
-          nd.leaf = (s.first << 3) | s.count;
-        }
-      },
-      [&](const TNode& n, int depth, float area, float parent_area) {
-        const bool inner2 = T[n.left].left >= 0 && T[n.right].left >= 0;
-        return !(depth < drop || (drop_sa > 0.f && inner2 && parent_area > 0.f && area > drop_sa * parent_area));
-      });
-}
-
-}  // namespace
-
-// error reporting for the other translation units of librtp.so
-rtp_status rtp_internal_fail(rtp_status st, const std::string& msg) {
-  g_err = msg;
-  return st;
-}
 
 namespace {
 // the device buffers and events every context owns from rtp_create on
@@ -428,9 +55,6 @@ rtp_status create_resources(rtp_context* c) {
 }  // namespace
 
 extern "C" {
-
-const char* rtp_last_error(void) { return g_err.c_str(); }
-int32_t rtp_abi_version(void) { return RTP_ABI_VERSION; }
 
 rtp_status rtp_create(int32_t device, rtp_context** out) {
   if (!out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_create: out is NULL");
@@ -473,305 +97,16 @@ void rtp_destroy(rtp_context* c) {
 
 // rtp_set_scene in steps: extract + buildBVH (MapperPathTracer.cxx:178-197,
 // 437-449) and the light coupling of the constructor (:141-148).  Every step
-// but the last works on the host only and may refuse the description; the
-// upload then replaces the context's scene.
+// but the last works on the host only and may refuse the description
+// (rtp_scene_host.cpp); the upload then replaces the context's scene.
 namespace {
 
-// what the steps hand on
-struct SceneBuild {
-  std::unique_ptr<rtp::DevScene> h{new rtp::DevScene()};  // the host image of the device scene
-  std::vector<int> kept;                                   // reference index of each kept quad
-  float blo[3], bhi[3];                                    // the quads' shape bounds (-direct mode)
-  std::vector<rtp::DevSphere> sph;
-  bool use_bvh = false, gpu_build = false;
-  float bvh_reach = 0.f;
-  std::vector<rtp::BvhNode> nodes;  // the host-built sphere BVH: 8 octant copies, and its leaf order's records
-  std::vector<rtp::DevSphereG> geom;
-  // the LDS walk's tree (kLdsWalkLeaf) in BvhNode form, its leaf order and size
-  std::vector<rtp::BvhNode> lw_nodes;
-  std::vector<int32_t> lw_order;
-  int lw_per_oct = 0;
-  // a mesh scene: its BVH (rtp_mesh_host.cpp) and the records it is uploaded as
-  bool mesh = false;
-  MeshBuild mb;
-  std::vector<uint32_t> mesh_cnodes;       // 8 * n_nodes compact nodes
-  std::vector<rtp::DevQuad> mesh_quads;    // leaf order
-  std::vector<float> mesh_shade;           // 8 floats per quad, the caller's order
-  // or, built on the device (rtp_mesh_gpu.hip): the arrays themselves, which scene_upload adopts
+// what the host steps built (rtp_scene.hpp), and for a mesh scene built on the
+// device (rtp_mesh_gpu.hip) the arrays themselves, which scene_upload adopts
+struct SceneUpload : SceneBuild {
   bool mesh_on_device = false;
   rtp::MeshGpuOut mesh_dev;
-
-  // the host image zeroed, every octant its own walk order (the device LBVH
-  // build keeps all 8; the host SAH build may narrow it, RTP_BVH_OCT_MASK)
-  rtp::DevScene* fresh() {
-    std::memset(h.get(), 0, sizeof(*h));
-    h->oct_mask = 7;
-    return h.get();
-  }
 };
-
-// (pt_ok, mat_ok, tex_ok: rtp_host_util.hpp, shared with the mesh builder)
-
-// The quads: validated, de-duplicated, grouped by kind, with the prefilter
-// tables and the -direct mode's bounds.  Quads that repeat an earlier quad
-// bit-for-bit (same vertices in the same order, same material and texture --
-// buildBox emits two such pairs per box, CornellBox.cpp:114-137) are dropped:
-// under the strict '<' closest test the later copy can never win, so the hit
-// record is unchanged.
-rtp_status scene_quads(const rtp_scene_desc* s, SceneBuild& B) {
-  if (s->n_points <= 0 || !s->points) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: no points");
-  if (s->n_quads < 0 || s->n_spheres < 0 || s->n_spheres > rtp::kMaxSpheresBvh)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: bad primitive counts");
-  if (s->n_spheres < 1)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: the light sphere radius is SphereRadii[0]; need >= 1 sphere");
-  rtp::DevScene* h = B.fresh();
-  std::vector<int>& kept = B.kept;
-  std::vector<rtp::DevQuad> built;
-  for (int q = 0; q < s->n_quads; q++) {
-    const int32_t* id = s->quad_points + 4 * q;
-    for (int k = 0; k < 4; k++)
-      if (!pt_ok(s, id[k])) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: quad point id out of range");
-    if (!mat_ok(s, s->quad_mat[q]) || !tex_ok(s, s->quad_tex[q]))
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: quad material/texture index out of range");
-    bool dup = false;
-    for (int j : kept) {
-      const int32_t* jd = s->quad_points + 4 * j;
-      bool same = s->quad_mat[j] == s->quad_mat[q] && s->quad_tex[j] == s->quad_tex[q];
-      for (int k = 0; k < 4 && same; k++) same = bit_equal(s->points + 3 * jd[k], s->points + 3 * id[k], 3);
-      if (same) {
-        dup = true;
-        break;
-      }
-    }
-    if (dup) continue;
-    if ((int)kept.size() >= rtp::kMaxQuads)
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: too many distinct quads");
-    rtp::DevQuad Q;
-    fill_quad(Q, s->points + 3 * id[0], s->points + 3 * id[1], s->points + 3 * id[2], s->points + 3 * id[3], false);
-    Q.mt = s->mat_type[s->quad_mat[q]];
-    st(Q.alb, ld(s->tex_rgb + 3 * s->tex_type[s->quad_tex[q]]));
-    Q.orig = (int32_t)kept.size();  // rank in the reference's (index) order
-    kept.push_back(q);
-    built.push_back(Q);
-  }
-  // group by kind (scan order 1..kQuadKinds-1, then 0); the device scan
-  // compares (t, orig) lexicographically, which is exactly the reference's
-  // index-order strict '<' scan, so the grouping changes no result.
-  {
-    int pos = 0;
-    for (int g = 0; g < rtp::kQuadKinds; g++) {
-      const int kind = (g + 1) % rtp::kQuadKinds;
-      h->kind_begin[g] = pos;
-      for (const rtp::DevQuad& Q : built)
-        if (Q.kind == kind) {
-          h->quads[pos] = Q;
-          h->quads[pos].key_lo = ((uint32_t)Q.orig << 8) | (uint32_t)pos;  // both < kMaxQuads = 256
-          pos++;
-        }
-    }
-    h->kind_begin[rtp::kQuadKinds] = pos;
-    if (env_is("RTP_VERBOSE", '1')) {
-      fprintf(stderr, "rtp: %d quads by scan group (kind: count / exact parallelograms):", pos);
-      for (int g = 0; g < rtp::kQuadKinds; g++) {
-        int np = 0;
-        for (int i = h->kind_begin[g]; i < h->kind_begin[g + 1]; i++) np += h->quads[i].para ? 1 : 0;
-        fprintf(stderr, " %d: %d/%d", (g + 1) % rtp::kQuadKinds, h->kind_begin[g + 1] - h->kind_begin[g], np);
-      }
-      fprintf(stderr, "\n");
-    }
-  }
-  setup_prefilter(h, s, kept);
-  h->n_quads = (int32_t)kept.size();
-  // the -direct mode's shape bounds (union of the quads' padded AABBs,
-  // AABBSurface.h:36-78)
-  float* blo = B.blo;
-  float* bhi = B.bhi;
-  for (int k = 0; k < 3; k++) blo[k] = INFINITY, bhi[k] = -INFINITY;
-  for (int q = 0; q < s->n_quads; q++) {
-    const int32_t* id = s->quad_points + 4 * q;
-    float mn[3], mx[3];
-    for (int k = 0; k < 3; k++) mn[k] = mx[k] = s->points[3 * id[0] + k];
-    for (int c2 = 1; c2 < 4; c2++)
-      for (int k = 0; k < 3; k++) {
-        const float v = s->points[3 * id[c2] + k];
-        mn[k] = (v < mn[k]) ? v : mn[k];  // vtkm::Min / Max: (std::min)/(std::max)
-        mx[k] = (mx[k] < v) ? v : mx[k];
-      }
-    for (int k = 0; k < 3; k++) {
-      const float ext = 1.0e-4f * (mx[k] - mn[k]);
-      const float eps = (1e-6f < ext) ? ext : 1e-6f;
-      mn[k] -= eps;
-      mx[k] += eps;
-      blo[k] = std::min(blo[k], mn[k]);
-      bhi[k] = std::max(bhi[k], mx[k]);
-    }
-  }
-  return RTP_OK;
-}
-
-// The sphere records, whether they get a BVH, its pad's reach and its builder.
-rtp_status scene_spheres(const rtp_scene_desc* s, SceneBuild& B) {
-  std::vector<rtp::DevSphere>& sph = B.sph;
-  sph.resize(s->n_spheres);
-  for (int k = 0; k < s->n_spheres; k++) {
-    if (!pt_ok(s, s->sphere_point[k]) || !mat_ok(s, s->sphere_mat[k]) || !tex_ok(s, s->sphere_tex[k]) ||
-        !(s->sphere_radius[k] > 0.0f))
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: sphere index or radius out of range");
-    rtp::DevSphere& S = sph[k];
-    std::memset(&S, 0, sizeof(S));
-    st(S.c, ld(s->points + 3 * s->sphere_point[k]));
-    S.r = s->sphere_radius[k];
-    S.rr = S.r * S.r;
-    S.mt = s->mat_type[s->sphere_mat[k]];
-    st(S.alb, ld(s->tex_rgb + 3 * s->tex_type[s->sphere_tex[k]]));
-  }
-  const bool use_bvh = B.use_bvh = s->n_spheres >= rtp::kBvhMinSpheres;
-  // The reach of the sphere boxes' pad (rtp_layout.hpp bvh_sphere_pad):
-  // kBvhReachFactor diagonals of the scene's bounding box -- every quad
-  // vertex, every sphere's c -+ r.
-  if (use_bvh) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    scene_bounds(s, true, lo, hi);
-    B.bvh_reach = rtp::scene_reach(lo, hi);
-  }
-  // which builder makes the sphere BVH: the host's binned SAH (better trees,
-  // O(n log n) on one core) or the device LBVH (rtp_bvh_gpu.hip) for large
-  // scenes; RTP_BVH_BUILD=host|gpu overrides
-  bool& gpu_build = B.gpu_build;
-  gpu_build = use_bvh && s->n_spheres >= rtp::kBvhGpuMinSpheres;
-  if (const char* bb = getenv("RTP_BVH_BUILD")) {
-    if (!std::strcmp(bb, "gpu")) gpu_build = use_bvh;
-    if (!std::strcmp(bb, "host")) gpu_build = false;
-  }
-  return RTP_OK;
-}
-
-// Where the spheres go: into the scene itself (few), or behind a BVH built on
-// the device at upload (many) or here -- the global walk's tree and, opt-in,
-// the LDS walk's.
-void scene_sphere_bvh(const rtp_scene_desc* s, SceneBuild& B) {
-  rtp::DevScene* h = B.h.get();
-  const std::vector<rtp::DevSphere>& sph = B.sph;
-  const float bvh_reach = B.bvh_reach;
-  std::vector<rtp::BvhNode>& nodes = B.nodes;
-  std::vector<rtp::DevSphereG>& geom = B.geom;
-  std::vector<rtp::BvhNode>& lw_nodes = B.lw_nodes;
-  std::vector<int32_t>& lw_order = B.lw_order;
-  int& lw_per_oct = B.lw_per_oct;
-  if (!B.use_bvh) {
-    for (int k = 0; k < s->n_spheres; k++) h->spheres[k] = sph[k];
-  } else if (B.gpu_build) {
-    h->n_nodes = 2 * s->n_spheres - 1;  // nodes and sphere records are built on the device (scene_upload)
-  } else {
-    std::vector<BvhPrim> P(s->n_spheres);
-    for (int k = 0; k < s->n_spheres; k++) {
-      const rtp::DevSphere& S = sph[k];
-      // (the slab test's margin and what float32 sphere_root accepts beyond
-      // the sphere: derived in rtp_layout.hpp; the same call in k_boxes)
-      const float pad = rtp::bvh_sphere_pad(S.c[0], S.c[1], S.c[2], S.r, bvh_reach);
-      for (int a = 0; a < 3; a++) {
-        P[k].lo[a] = S.c[a] - S.r - pad;
-        P[k].hi[a] = S.c[a] + S.r + pad;
-        P[k].cen[a] = S.c[a];
-      }
-      P[k].idx = k;
-    }
-    const std::vector<BvhPrim> P0 = P;  // (bvh_build reorders P)
-    std::vector<int32_t> order;
-    std::vector<TNode> tree;
-    bvh_build(P, 0, s->n_spheres, tree, order);
-    // inner nodes above this depth are not emitted (bvh_flatten; RTP_BVH_DROP overrides)
-    int drop = kBvhDropDepth;
-    float drop_sa = kBvhDropArea;
-    if (const char* dd = getenv("RTP_BVH_DROP")) drop = std::max(0, std::min(16, atoi(dd)));
-    if (const char* da = getenv("RTP_BVH_DROP_SA")) drop_sa = (float)atof(da);
-    // the copies the walk reads: octant o walks copy (o & oct_mask)
-    // (RTP_BVH_OCT_MASK; the other copies are built the same and never read)
-    int oct_mask = 7;
-    if (const char* om = getenv("RTP_BVH_OCT_MASK")) oct_mask = atoi(om) & 7;
-    h->oct_mask = oct_mask;
-    int per_oct = 0;
-    for (int oct = 0; oct < 8; oct++) {  // 8 copies of n_nodes entries, indices local to each copy
-      std::vector<rtp::BvhNode> one;
-      bvh_flatten(tree, 0, oct & oct_mask, order, sph, one, drop, drop_sa);
-      per_oct = (int)one.size();  // (the same nodes are dropped in every octant's order)
-      nodes.insert(nodes.end(), one.begin(), one.end());
-    }
-    // The LDS walk's tree (opt-in, RTP_BVH_LDS=1): leaves of up to
-    // kLdsWalkLeaf spheres, flattened the same way, used when its 8 copies
-    // plus the leaf spheres fit the block's LDS (the stats build and planned
-    // launches walk the global tree).  On C3 at 16 spp (r04h/r04i, kernel ms):
-    // LDS walk 324, the global walk over the same leaves-of-6 tree 349, the
-    // global walk over the leaves-of-1 tree 186 -- the LDS copy saves 7% of the
-    // texture-path gathers' cost, the bigger leaves it needs to fit cost 88%
-    // (10 exact sphere tests per ray instead of 4: DESIGN.md 4.2).
-    if (env_is("RTP_BVH_LDS", '1')) {
-      std::vector<BvhPrim> P2 = P0;
-      std::vector<TNode> tree2;
-      bvh_build(P2, 0, s->n_spheres, tree2, lw_order, rtp::kLdsWalkLeaf);
-      for (int oct = 0; oct < 8; oct++) {
-        std::vector<rtp::BvhNode> one;
-        bvh_flatten(tree2, 0, oct, lw_order, sph, one, drop, drop_sa);
-        lw_per_oct = (int)one.size();
-        lw_nodes.insert(lw_nodes.end(), one.begin(), one.end());
-      }
-      const int64_t bytes = (int64_t)16 * (8 * (int64_t)lw_per_oct + (int64_t)lw_order.size());
-      if (bytes > rtp_lds_walk_capacity()) {
-        lw_nodes.clear();
-        lw_order.clear();
-        lw_per_oct = 0;
-      }
-    }
-    geom.resize(order.size());
-    for (size_t j = 0; j < order.size(); j++) {
-      const rtp::DevSphere& S = sph[order[j]];
-      std::memset(&geom[j], 0, sizeof(geom[j]));
-      std::memcpy(geom[j].c, S.c, sizeof(S.c));
-      geom[j].rr = S.rr;
-      geom[j].orig = order[j];
-    }
-    h->n_nodes = (int32_t)per_oct;
-  }
-  h->n_spheres = s->n_spheres;
-}
-
-// lights (MapperPathTracer.cxx:141-148): light quad = light_box_pointids[1..4];
-// the glass constants and the `which` thresholds
-rtp_status scene_lights(const rtp_scene_desc* s, SceneBuild& B) {
-  rtp::DevScene* h = B.h.get();
-  const int32_t* lq = s->light_quad_points;
-  for (int k = 0; k < 4; k++)
-    if (!pt_ok(s, lq[k])) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light quad point id out of range");
-  if (!pt_ok(s, s->light_sphere_point))
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: light sphere point id out of range");
-  v3 q = ld(s->points + 3 * lq[0]), r = ld(s->points + 3 * lq[1]), ss = ld(s->points + 3 * lq[2]),
-     t = ld(s->points + 3 * lq[3]);
-  fill_quad(h->light.quad, &q.x, &r.x, &ss.x, &t.x, false);
-  {
-    float qr = std::sqrt(dot(sub(r, q), sub(r, q)));  // vtkm::Magnitude
-    float qt = std::sqrt(dot(sub(t, q), sub(t, q)));
-    h->light.area = qr * qt;  // PdfWorklet.h:236-239
-  }
-  // QuadWorkletGenerateDir uses pts[pointIndex[1]] and pts[pointIndex[3]]
-  {
-    float x0 = q.x, x1 = ss.x, z0 = q.z, z1 = ss.z, y0 = q.y, y1 = q.y;
-    h->light.gx0 = x0, h->light.gdx = x1 - x0;
-    h->light.gy0 = y0, h->light.gdy = y1 - y0;
-    h->light.gz0 = z0, h->light.gdz = z1 - z0;
-  }
-  st(h->light.sc, ld(s->points + 3 * s->light_sphere_point));
-  h->light.sr = s->sphere_radius[0];  // SphereRadii[0] (PdfWorklet.h:205-210)
-  h->light.srr = h->light.sr * h->light.sr;
-  h->ior = s->ior;
-  {  // schlick's r0^2 and 1/ior with the reference's operations (float, float; double then float)
-    float r0 = (1 - h->ior) / (1 + h->ior);
-    h->ior_r0sq = r0 * r0;
-    h->ior_inv = (float)(1.0 / h->ior);
-  }
-  h->which_t1 = which_threshold(2);
-  h->which_t2 = which_threshold(3);
-  return RTP_OK;
-}
 
 #define UPLOAD_TRY(expr) HIP_TRY_AS("rtp_set_scene upload", expr)
 
@@ -841,7 +176,7 @@ rtp_status upload_bvh_host(rtp_context* c, SceneBuild& B) {
 // until the new DevScene is on the device the context has no scene: an upload
 // that fails leaves it answering RTP_ERR_NO_SCENE (the arrays it did allocate
 // stay the context's and go with the next rtp_set_scene or rtp_destroy).
-rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneBuild& B) {
+rtp_status scene_upload(rtp_context* c, const rtp_scene_desc* s, SceneUpload& B) {
   rtp::DevScene* h = B.h.get();
   UPLOAD_TRY(hipSetDevice(c->device));
   if (c->pending) {  // a queued render may still read the old scene
@@ -972,7 +307,7 @@ rtp_status set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, hipStr
   hs.sphere_point = sphere_point;
   hs.quad_points = hs.quad_mat = hs.quad_tex = nullptr;
   // the reach: mesh_build's, over the device's exact min / max of the quads' vertices and the spheres' c -+ r
-  SceneBuild B;
+  SceneUpload B;
   B.mesh = true;
   {
     float lo[3], hi[3];
@@ -983,7 +318,7 @@ rtp_status set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, hipStr
   }
   rtp::DevScene* h = B.fresh();
   RTP_TRY(scene_spheres(&hs, B));
-  scene_sphere_bvh(&hs, B);
+  scene_sphere_bvh(&hs, B, rtp_lds_walk_capacity());
   RTP_TRY(scene_lights(&hs, B));
   int32_t open_tree = 0;
   UPLOAD_TRY(rtp_mesh_gpu_build(&in, B.mb.reach, &B.mesh_dev, &open_tree, stream));
@@ -1026,10 +361,10 @@ extern "C" {
 
 rtp_status rtp_set_scene(rtp_context* c, const rtp_scene_desc* s) {
   if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene: NULL argument");
-  SceneBuild B;
+  SceneUpload B;
   RTP_TRY(scene_quads(s, B));
   RTP_TRY(scene_spheres(s, B));
-  scene_sphere_bvh(s, B);
+  scene_sphere_bvh(s, B, rtp_lds_walk_capacity());
   RTP_TRY(scene_lights(s, B));
   return scene_upload(c, s, B);
 }
@@ -1043,12 +378,12 @@ rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
   // RTP_MESH_BUILD=gpu: the device build from these host arrays (the A/B handle, like RTP_BVH_BUILD)
   if (const char* mb = getenv("RTP_MESH_BUILD"))
     if (!std::strcmp(mb, "gpu")) return set_scene_mesh_uploaded(c, s);
-  SceneBuild B;
+  SceneUpload B;
   B.mesh = true;
   RTP_TRY(mesh_build(s, B.mb));
   rtp::DevScene* h = B.fresh();
   RTP_TRY(scene_spheres(s, B));  // (fewer than kBvhMinSpheres: no sphere BVH)
-  scene_sphere_bvh(s, B);
+  scene_sphere_bvh(s, B, rtp_lds_walk_capacity());
   RTP_TRY(scene_lights(s, B));
   mesh_records(s, B.mb, B.mesh_quads, B.mesh_shade);
   B.mesh_cnodes.resize((size_t)4 * B.mb.nodes.size());
@@ -1063,45 +398,6 @@ rtp_status rtp_set_scene_mesh(rtp_context* c, const rtp_scene_desc* s) {
 rtp_status rtp_set_scene_mesh_device(rtp_context* c, const rtp_scene_desc* s, void* hip_stream) {
   if (!c || !s) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_scene_mesh_device: NULL argument");
   return set_scene_mesh_device(c, s, static_cast<hipStream_t>(hip_stream));
-}
-
-// test hook (rtp_mesh.hpp): the current mesh scene as its builder left it
-rtp_status rtp_debug_mesh_readback(rtp_context* c, int32_t oct, int32_t node_cap, int32_t* n_nodes, void* cnodes,
-                                   int32_t* order, float* boxes, float* pads) {
-  if (!c || !c->has_scene || !c->is_mesh)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: the context holds no mesh scene");
-  if (oct < 0 || oct > 7) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: octant outside 0..7");
-  HIP_TRY(hipSetDevice(c->device));
-  RTP_TRY(drain(c));
-  const size_t nn = (size_t)c->n_mesh_nodes, nq = (size_t)c->n_mesh_quads;
-  if (n_nodes) *n_nodes = c->n_mesh_nodes;
-  if (cnodes) {
-    if (node_cap < c->n_mesh_nodes)
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_readback: node_cap too small");
-    HIP_TRY(hipMemcpy(cnodes, c->d_mesh_nodes + 4 * nn * (size_t)oct, 16 * nn, hipMemcpyDeviceToHost));
-  }
-  if (order)
-    HIP_TRY(hipMemcpy2D(order, sizeof(int32_t), reinterpret_cast<const char*>(c->d_mesh_quads) + offsetof(rtp::DevQuad, orig),
-                        sizeof(rtp::DevQuad), sizeof(int32_t), nq, hipMemcpyDeviceToHost));
-  if (c->d_mesh_boxes) {
-    HIP_TRY(DevBufs::back(boxes, c->d_mesh_boxes, 24 * nq));
-    HIP_TRY(DevBufs::back(pads, c->d_mesh_pads, 4 * nq));
-  } else {
-    if (boxes) std::memcpy(boxes, c->h_mesh_boxes.data(), 24 * nq);
-    if (pads) std::memcpy(pads, c->h_mesh_pads.data(), 4 * nq);
-  }
-  return RTP_OK;
-}
-
-// test hook (rtp_mesh.hpp): the stored records of the current mesh scene, whole, in leaf order
-rtp_status rtp_debug_mesh_records(rtp_context* c, int64_t cap, void* records) {
-  if (!c || !c->has_scene || !c->is_mesh)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_records: the context holds no mesh scene");
-  if (!records || cap < c->n_mesh_quads) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_mesh_records: cap too small");
-  HIP_TRY(hipSetDevice(c->device));
-  RTP_TRY(drain(c));
-  HIP_TRY(hipMemcpy(records, c->d_mesh_quads, sizeof(rtp::DevQuad) * (size_t)c->n_mesh_quads, hipMemcpyDeviceToHost));
-  return RTP_OK;
 }
 
 rtp_status rtp_mesh_guarantee(rtp_context* c, float* cos_min, float* reach) {
@@ -1130,22 +426,6 @@ rtp_status refuse_mesh(const rtp_context* c, const char* who) {
   if (c && c->has_scene && c->is_mesh)
     return fail(RTP_ERR_INVALID_ARGUMENT, std::string(who) + ": not available on a mesh scene (rtp_set_scene_mesh)");
   return RTP_OK;
-}
-
-// pathtracing::Camera::SetParameters -> CreateRaysImpl -> RayGen ctor
-void camera_setup(const rtp_camera* cam, int32_t nx, int32_t ny, rtp::DevCamera* out) {
-  v3 up = ld(cam->view_up);
-  if (!(up.x == 0.f && up.y == 1.f && up.z == 0.f)) up = normalize(up);  // SetUp (Camera.cxx:767-776)
-  v3 pos = ld(cam->position);
-  v3 look = normalize(sub(ld(cam->look_at), pos));  // Camera.cxx:908-909
-  float thx = tanf((cam->fov_y_deg * kPi180f) * .5f);
-  float thy = tanf((cam->fov_y_deg * kPi180f) * .5f);
-  v3 u = normalize(cross(look, up));
-  v3 v = normalize(cross(u, look));
-  st(out->eye, pos);
-  st(out->dx, scl(u, (2 * thx / (float)nx)));
-  st(out->dy, scl(v, (2 * thy / (float)ny)));
-  st(out->nlook, normalize(look));
 }
 
 rtp_status check_render_args(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, int32_t spp,
@@ -1693,230 +973,6 @@ rtp_status rtp_render_guides(rtp_context* c, const rtp_camera* cam, int32_t nx, 
   HIP_TRY_AS("render_guides: copy back", DevBufs::back(g1, d_g1, 16 * n));
   HIP_TRY_AS("render_guides: copy back", DevBufs::back(prim, d_prim, 4 * n));
   fill_stats(stats, n, ms);
-  return RTP_OK;
-}
-
-// Diagnostics: sums of the pool kernel's per-wave counters from the last launch
-// made with RTP_DEBUG_STATS=1 (order of rtp::DbgCounter); returns the number
-// of waves, 0 if none were recorded.
-int32_t rtp_debug_counters(rtp_context* c, uint64_t* out, int32_t n_out) {
-  if (!c || !c->d_dbg || !out) return 0;
-  std::vector<unsigned long long> h((size_t)c->dbg_waves * rtp::kDbgCounters);
-  if (hipMemcpy(h.data(), c->d_dbg, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  if (n_out < 0) {  // raw per-wave records: out must hold waves * kDbgCounters values
-    std::memcpy(out, h.data(), h.size() * 8);
-    return c->dbg_waves;
-  }
-  for (int k = 0; k < n_out && k < rtp::kDbgCounters; k++) {
-    uint64_t acc = 0;
-    for (int w = 0; w < c->dbg_waves; w++) acc += h[(size_t)w * rtp::kDbgCounters + k];
-    out[k] = acc;
-  }
-  if (n_out > rtp::kDbgCounters) {  // extra slot: max wave lifetime
-    uint64_t mx = 0;
-    for (int w = 0; w < c->dbg_waves; w++) mx = std::max<uint64_t>(mx, h[(size_t)w * rtp::kDbgCounters + rtp::kDbgCyclesTotal]);
-    out[rtp::kDbgCounters] = mx;
-  }
-  return c->dbg_waves;
-}
-
-rtp_status rtp_eval_primitive(rtp_context* c, int32_t kind, const void* in, void* out, int64_t n) {
-  if (!c || !in || !out || n < 0 || kind < 0 || kind > 7)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_eval_primitive: bad arguments");
-  if (n == 0) return RTP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  const uint32_t* tab = nullptr;
-  if (kind == 4 || kind == 5 || kind == 7) {
-    const FfSnap ft = ff_tables(c->device, c->ff_policy, 0);
-    tab = kind == 4 ? ft.t[1] : kind == 5 ? ft.t[0] : ft.direct;  // 16 / 32 dead depths, direct_first
-    if (!tab) return fail(RTP_ERR_DEVICE, "rtp_eval_primitive: RNG jump tables are not built (policy or memory)");
-  }
-  const int dk = kind <= 3 ? kind : (kind == 6 ? 5 : 4);  // device kinds: 4 gather, 5 one dead step
-  DevBufs b;
-  void *din = nullptr, *dout = nullptr;
-  HIP_TRY_AS("rtp_eval_primitive", b.get(&din, (size_t)n * 4, in));
-  HIP_TRY_AS("rtp_eval_primitive", b.get(&dout, (size_t)n * 4));
-  HIP_TRY_AS("rtp_eval_primitive",
-             rtp_launch_eval_primitive(dk, din, dout, n, tab, which_threshold(2), which_threshold(3), nullptr));
-  HIP_TRY_AS("rtp_eval_primitive", DevBufs::back(out, dout, (size_t)n * 4));
-  return RTP_OK;
-}
-
-// Diagnostics: the closest hit of host rays with and without the quad
-// prefilter (rtp_eval_closest_kernel; 7 u32 per ray).
-rtp_status rtp_debug_closest_hit(rtp_context* c, const float* rays, int64_t n, uint32_t* out) {
-  if (!c || !rays || !out || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_closest_hit: bad arguments");
-  // (has_scene, not d_scene: the device scene exists from rtp_create on, and
-  // names freed arrays after an rtp_set_scene whose upload failed)
-  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "rtp_debug_closest_hit: no scene set");
-  if (n == 0) return RTP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  DevBufs b;
-  float* din = nullptr;
-  uint32_t* dout = nullptr;
-  HIP_TRY_AS("rtp_debug_closest_hit", b.get(&din, (size_t)n * 24, rays));
-  HIP_TRY_AS("rtp_debug_closest_hit", b.get(&dout, (size_t)n * 28));
-  HIP_TRY_AS("rtp_debug_closest_hit", rtp_launch_eval_closest(c->d_scene, din, dout, n, c->is_mesh ? 3 : c->use_bvh ? 1 : 0, nullptr));
-  HIP_TRY_AS("rtp_debug_closest_hit", DevBufs::back(out, dout, (size_t)n * 28));
-  return RTP_OK;
-}
-
-// Diagnostics: one depth of the path kernel's bounce() for host rays and
-// seeds (rtp_eval_bounce_kernel; 15 u32 per ray).
-rtp_status rtp_debug_bounce(rtp_context* c, const float* rays, const uint32_t* seeds, int64_t n, uint32_t* out) {
-  if (!c || !rays || !seeds || !out || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_bounce: bad arguments");
-  if (!c->has_scene) return fail(RTP_ERR_NO_SCENE, "rtp_debug_bounce: no scene set");
-  if (n == 0) return RTP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  DevBufs b;
-  float* din = nullptr;
-  uint32_t* dseed = nullptr;
-  uint32_t* dout = nullptr;
-  HIP_TRY_AS("rtp_debug_bounce", b.get(&din, (size_t)n * 24, rays));
-  HIP_TRY_AS("rtp_debug_bounce", b.get(&dseed, (size_t)n * 4, seeds));
-  HIP_TRY_AS("rtp_debug_bounce", b.get(&dout, (size_t)n * 60));
-  HIP_TRY_AS("rtp_debug_bounce", rtp_launch_eval_bounce(c->d_scene, din, dseed, dout, n, c->is_mesh ? 3 : c->use_bvh ? 1 : 0, nullptr));
-  HIP_TRY_AS("rtp_debug_bounce", DevBufs::back(out, dout, (size_t)n * 60));
-  return RTP_OK;
-}
-
-// Diagnostics: the render kernels' camera_ray for host rows of (pixel, seed)
-// under the DevCamera a render of this camera and canvas would launch with
-// (rtp_eval_raygen_kernel; 12 u32 of camera constants, then 5 u32 per row).
-rtp_status rtp_debug_raygen(rtp_context* c, const rtp_camera* cam, int32_t nx, int32_t ny, const int64_t* pixels,
-                            const uint32_t* seeds, int64_t n, uint32_t* out) {
-  if (!c || !cam || !out || n < 0 || (n > 0 && (!pixels || !seeds)))
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_raygen: bad arguments");
-  RTP_TRY(check_canvas_camera(c, cam, nx, ny, "rtp_debug_raygen"));
-  for (int64_t i = 0; i < n; i++)
-    if (pixels[i] < 0 || pixels[i] >= (int64_t)nx * ny)
-      return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_debug_raygen: pixel outside the canvas");
-  rtp::DevCamera dc;
-  camera_setup(cam, nx, ny, &dc);
-  static_assert(sizeof(dc) == 48, "eye, nlook, delta_x, delta_y");
-  std::memcpy(out, &dc, sizeof(dc));
-  if (n == 0) return RTP_OK;
-  HIP_TRY(hipSetDevice(c->device));
-  DevBufs b;
-  int64_t* dpix = nullptr;
-  uint32_t* dseed = nullptr;
-  uint32_t* dout = nullptr;
-  HIP_TRY_AS("rtp_debug_raygen", b.get(&dpix, (size_t)n * 8, pixels));
-  HIP_TRY_AS("rtp_debug_raygen", b.get(&dseed, (size_t)n * 4, seeds));
-  HIP_TRY_AS("rtp_debug_raygen", b.get(&dout, (size_t)n * 20));
-  HIP_TRY_AS("rtp_debug_raygen", rtp_launch_eval_raygen(&dc, nx, ny, dpix, dseed, dout, n, nullptr));
-  HIP_TRY_AS("rtp_debug_raygen", DevBufs::back(out + 12, dout, (size_t)n * 20));
-  return RTP_OK;
-}
-
-int32_t rtp_sphere_walk(rtp_context* c) {
-  if (!c || !c->has_scene || !c->use_bvh) return 0;
-  return c->lw_bytes > 0 ? 2 : 1;
-}
-
-int32_t rtp_sphere_walk_oct_mask(rtp_context* c) {
-  if (!c || !c->has_scene || !c->use_bvh) return -1;
-  // the value the kernels read: DevScene::oct_mask of the device copy (the
-  // host field is a mirror, checked against it)
-  int32_t dm = -1;
-  if (hipSetDevice(c->device) != hipSuccess ||
-      hipMemcpy(&dm, reinterpret_cast<const char*>(c->d_scene) + offsetof(rtp::DevScene, oct_mask), sizeof(dm),
-                hipMemcpyDeviceToHost) != hipSuccess)
-    return -2;
-  return dm == c->oct_mask ? dm : -3;
-}
-
-// Diagnostics: exhaustive device check of a fast arithmetic sequence (kind,
-// see rtp_verify_fast_math_kernel) over float bit patterns [lo_bits, hi_bits].
-rtp_status rtp_verify_fast_math(rtp_context* c, int32_t kind, uint32_t lo_bits, uint32_t hi_bits,
-                                uint64_t* mismatches, uint32_t* first_bad) {
-  if (!c || !mismatches || hi_bits < lo_bits || kind < 0 || kind > 8)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_verify_fast_math: bad args");
-  HIP_TRY(hipSetDevice(c->device));
-  unsigned long long* d_bad = nullptr;
-  uint32_t* d_first = nullptr;
-  HIP_TRY(hipMalloc(&d_bad, 8));
-  HIP_TRY(hipMalloc(&d_first, 4));
-  HIP_TRY(hipMemset(d_bad, 0, 8));
-  HIP_TRY(hipMemset(d_first, 0xff, 4));
-  const uint64_t total = (uint64_t)hi_bits - lo_bits + 1;
-  const uint64_t chunk = 1ull << 30;
-  for (uint64_t off = 0; off < total; off += chunk) {
-    const uint64_t n = std::min<uint64_t>(chunk, total - off);
-    HIP_TRY(rtp_launch_verify_fast_math(kind, lo_bits + (uint32_t)off, n, d_bad, d_first, nullptr));
-  }
-  unsigned long long bad = 0;
-  uint32_t first = 0;
-  HIP_TRY(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&first, d_first, 4, hipMemcpyDeviceToHost));
-  (void)hipFree(d_bad);
-  (void)hipFree(d_first);
-  *mismatches = bad;
-  if (first_bad) *first_bad = first;
-  return RTP_OK;
-}
-
-rtp_status rtp_set_ff_tables(rtp_context* c, int32_t policy) {
-  if (!c || policy < RTP_FF_TABLES_AUTO || policy > RTP_FF_TABLES_ON)
-    return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_set_ff_tables: bad arguments");
-  c->ff_policy = policy;
-  if (policy == RTP_FF_TABLES_ON) {
-    HIP_TRY(hipSetDevice(c->device));
-    (void)ff_tables(c->device, policy, 0);  // build now, outside any timed render
-  }
-  return RTP_OK;
-}
-
-rtp_status rtp_get_ff_tables(rtp_context* c, rtp_ff_info* out) {
-  if (!c || !out) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_get_ff_tables: bad arguments");
-  std::lock_guard<std::mutex> lk(g_ff_mu);
-  const FfTables& T = g_ff[c->device & 63];
-  *out = rtp_ff_info{};
-  out->policy = c->ff_policy;
-  out->built = T.d_count > 0 ? 2 : T.n_chain > 0 ? 1 : 0;
-  out->chain_tables = T.n_chain;
-  out->direct_first = T.d_first;
-  out->direct_count = T.d_count;
-  out->bytes = T.bytes;
-  out->alloc_ms = T.alloc_ms;
-  out->build_ms = T.build_ms;
-  out->samples_seen = T.samples_seen;
-  uint64_t chain = 0, direct = 0;
-  ff_auto_samples(chain, direct, &T);
-  out->auto_samples = chain;
-  out->auto_samples_direct = direct;
-  return RTP_OK;
-}
-
-// NormalizeFunctor (main.cc:253-287): de-NaN rgb, then sqrt(c / spp) on all
-// four channels.
-rtp_status rtp_normalize(float* rgba, int64_t n, int32_t spp) {
-  if (!rgba || n < 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_normalize: bad arguments");
-  const float samplecount = (float)spp;
-  for (int64_t i = 0; i < n; i++) {
-    float* px = rgba + 4 * i;
-    for (int k = 0; k < 3; k++)
-      if (!(px[k] == px[k])) px[k] = 0;
-    for (int k = 0; k < 4; k++) px[k] = std::sqrt(px[k] / samplecount);
-  }
-  return RTP_OK;
-}
-
-// save() (main.cc:325-384): P3 header "nx ny 255", one "r g b" line per
-// pixel in buffer order (row 0 = camera bottom), int(255.99*c) unclamped,
-// NaN pixels written as 0.
-rtp_status rtp_write_pnm(const char* path, const float* rgba, int32_t nx, int32_t ny) {
-  if (!path || !rgba || nx <= 0 || ny <= 0) return fail(RTP_ERR_INVALID_ARGUMENT, "rtp_write_pnm: bad arguments");
-  FILE* f = std::fopen(path, "w");
-  if (!f) return fail(RTP_ERR_INVALID_ARGUMENT, std::string("Couldn't save pnm: ") + path);
-  std::fprintf(f, "P3\n%d %d 255\n", nx, ny);
-  const int64_t n = (int64_t)nx * ny;
-  for (int64_t i = 0; i < n; i++) {
-    float c[3] = {rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2]};
-    if ((c[0] != c[0]) || (c[1] != c[1]) || (c[2] != c[2])) c[0] = c[1] = c[2] = 0.0f;
-    std::fprintf(f, "%d %d %d\n", (int)(255.99 * c[0]), (int)(255.99 * c[1]), (int)(255.99 * c[2]));
-  }
-  std::fclose(f);
   return RTP_OK;
 }
 

@@ -1,5 +1,5 @@
 // rtp_layout.hpp -- device-resident scene and launch-parameter layout shared by
-// the host (rtp_host.cpp) and the HIP kernels (rtp_kernels.hip).
+// the host (built by rtp_scene_host.cpp, uploaded by rtp_host.cpp) and the HIP kernels (rtp_kernels.hip).
 //
 // Everything here is RAY-INDEPENDENT data precomputed once on the host with
 // the same float operations the reference performs per ray (edge vectors,
@@ -105,14 +105,14 @@ static_assert(sizeof(DevSphereG) == 32 && offsetof(DevSphereG, orig) == 16, "sph
 // Threaded (stackless) BVH node in depth-first order: on a hit of an inner
 // node traversal continues at i+1 (its left child); on a miss, or after a
 // leaf, at `skip` (the first node after this subtree; n_nodes ends the walk).
-// The boxes are padded so that culling is conservative (rtp_host.cpp).
+// The boxes are padded so that culling is conservative (rtp_scene_host.cpp).
 struct alignas(16) BvhNode {
   float lo[3];
   int32_t skip;
   float hi[3];
   int32_t leaf;  // 0: inner; kBvhLeafSphere: one embedded sphere; else (first << 3) | count
 };
-// The pad of a sphere's box (both builders: rtp_host.cpp rtp_set_scene,
+// The pad of a sphere's box (both builders: rtp_scene_host.cpp scene_sphere_bvh,
 // rtp_bvh_gpu.hip k_boxes).  The boxes only cull, which is sound only if
 // every ray that the float32 sphere_root (rtp_kernels.hip) accepts for a
 // sphere crosses every box around it, and the point at the accepted t lies in
@@ -443,7 +443,7 @@ struct KParams {
   unsigned long long* progress;  // 2 words zeroed before launch: [0] samples finished by all waves (issue-priority
                                  // balancing), [1] entries claimed by work stealing (pool kernel kSteal)
   // RNG jump tables (nullable): ff[j][s] = the state after (32 >> j) dead
-  // depths from state s (2^32 entries each, 16 GiB; rtp_host.cpp)
+  // depths from state s (2^32 entries each, 16 GiB; rtp_ff_host.cpp)
   const uint32_t* ff[kFfTables];
   // direct tables (nullable): ffd[(r - ffd_first) << 32 | s] = the state after
   // r dead depths from s, for r in [ffd_first, ffd_first + ffd_count)

@@ -65,7 +65,7 @@ extern "C" int32_t rtp_mesh_leaf_size(void);
 extern "C" void rtp_mesh_compact_host(const void* nodes, int64_t n, uint32_t* out);
 extern "C" rtp_status rtp_mesh_scan_host(const rtp_scene_desc* scene, const float* rays, int64_t n, uint32_t* out);
 // The context's current mesh scene as its builder left it, host or device
-// (rtp_host.cpp): octant `oct`'s compact nodes (16 bytes each, at most
+// (rtp_debug_host.cpp): octant `oct`'s compact nodes (16 bytes each, at most
 // node_cap), the leaf order (DevQuad::orig of each stored quad), and each
 // quad's padded box (6 floats) and pad in the caller's order.  Every output is
 // optional.

@@ -1,6 +1,6 @@
 // rtp_mesh_cell.hpp -- the arithmetic of one mesh cell, stated once for the
 // host builder (rtp_mesh_host.cpp), the device builder (rtp_mesh_gpu.hip) and
-// the inline scene's quads (rtp_host.cpp): the float helpers whose results the
+// the inline scene's quads (rtp_scene_host.cpp): the float helpers whose results the
 // two builders must share bit for bit, a cell's pad and padded box
 // (rtp_layout.hpp kMeshCosMin has the derivation), its DevQuad record, and the
 // outward rounding to half precision of the walks' compact nodes.

@@ -11,8 +11,7 @@
 #include <string>
 
 #include "rtp_bvh_host.hpp"
-#include "rtp_context.hpp"
-#include "rtp_host_util.hpp"
+#include "rtp_host_base.hpp"
 #include "rtp_mesh.hpp"
 
 namespace rtp_host {

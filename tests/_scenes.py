@@ -432,7 +432,7 @@ VARIANTS = {
 def kept_quads(z):
     """Scene indices of the quads the host keeps: a quad that repeats an
     earlier one bit for bit (vertices in order, material, texture) is dropped
-    (rtp_host.cpp rtp_set_scene)."""
+    (rtp_scene_host.cpp scene_quads)."""
     V = z.verts()
     seen, kept = set(), []
     for q in range(len(z.quads)):
@@ -445,7 +445,7 @@ def kept_quads(z):
 
 def prefilter_expected(z):
     """Whether the closest-hit prefilter is on for z, from the gates'
-    definition (rtp_host.cpp setup_prefilter): between 1 and MAX_PRE
+    definition (rtp_scene_host.cpp setup_prefilter): between 1 and MAX_PRE
     axis-plane quads among the kept ones, none of their vertex coordinates
     beyond PRE_LIM."""
     pairs = z.classify()

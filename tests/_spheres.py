@@ -5,7 +5,7 @@ constants): no GPU.
 
 Everything the library computes is restated here from its definition, never
 imported: the float32 sphere root (rtp_kernels.hip sphere_root, the oracle's
-sphere_hit), the pad of a sphere's box (rtp_host.cpp rtp_set_scene,
+sphere_hit), the pad of a sphere's box (rtp_scene_host.cpp scene_sphere_bvh,
 rtp_bvh_gpu.hip k_boxes; the pad before the soundness bound is kept as
 pad_old for the guard that shows what that bound is for) and the outward
 rounding to half precision (rtp_mesh_cell.hpp half_outward).

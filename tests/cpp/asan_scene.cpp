@@ -1,11 +1,13 @@
 // asan_scene.cpp -- the C ABI's scene and render entry points under the host
 // AddressSanitizer + UBSan (built by build.build_asan(): every host
-// translation unit of librtp -- rtp_host.cpp, rtp_direct_host.cpp,
+// translation unit of librtp -- rtp_host.cpp and the other *_host.cpp units,
 // scene_cornell.cpp and the launch stubs of the .hip files -- compiled with
 // -Xarch_host -fsanitize=address,undefined; device code unchanged).
 //
 // Without a HIP device: rtp_create must fail with RTP_ERR_DEVICE and the
-// host-only helpers (scene tables, normalise, PNM) run sanitized.
+// host-only helpers (scene tables, normalise, PNM) run sanitized; the scene
+// build behind rtp_set_scene (rtp_scene_host.cpp) runs sanitized without a
+// device in scene_build_check.cpp.
 // With one: the scene replacements the reference's ctor/SetData sequence can
 // produce (MapperPathTracer.cxx:100-140 builds the scene per mapper), i.e.
 // Cornell -> the C3 sphere BVH (host SAH and device LBVH) -> Cornell, each

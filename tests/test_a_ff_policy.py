@@ -57,7 +57,7 @@ def test_policy_auto_direct_stage_follows_measured_allocation():
     fresh child process.  The chain tables come with the 12th frame (7.5e9
     samples); from then on the direct stage's break-even is the chain stage's
     count + (0.07 s + 2.5x the chain tables' measured allocation time) /
-    1.23e-11 s per sample (rtp_host.cpp ff_auto_samples), and the direct
+    1.23e-11 s per sample (rtp_ff_host.cpp ff_auto_samples), and the direct
     block is built on the frame that reaches it."""
     import json
     import subprocess

@@ -174,7 +174,7 @@ def test_lds_walk_equals_global_walk_c3(rtp, device, monkeypatch):
 @pytest.mark.parametrize("drop", [0, 1, 3, 8])
 def test_dropped_top_nodes_match_oracle(rtp, oracle, device, monkeypatch, drop, walk):
     """Inner nodes above depth `drop` left out of the walks' arrays
-    (rtp_host.cpp bvh_flatten, RTP_BVH_DROP): their boxes count as hit, so the
+    (rtp_scene_host.cpp bvh_flatten, RTP_BVH_DROP): their boxes count as hit, so the
     walk visits more nodes but finds the same (t, index) minimum -- bit-exact
     against the oracle's brute-force closest hit (900 spheres, both walks; 8
     drops most of the tree's inner levels)."""

@@ -1,4 +1,4 @@
-"""RNG jump tables (rtp_host.cpp, one fused build kernel): the state after 32 /
+"""RNG jump tables (rtp_ff_host.cpp, one fused build kernel): the state after 32 /
 16 / ... dead depths (chain tables) and after each count of the direct block,
 for every 32-bit state.  Checked on random states against an independent
 numpy restatement of the dead-depth draw sequence (which draw, then 2 or 3

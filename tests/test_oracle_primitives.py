@@ -64,7 +64,7 @@ def _which_threshold(oracle, w):
 
 def test_which_is_a_two_threshold_step_function(oracle):
     """which = min(3, int(r*3+1)) is monotone in the hash, so the device can
-    decide it with two integer compares (rtp_host.cpp which_threshold)."""
+    decide it with two integer compares (rtp_scene_host.cpp which_threshold)."""
     L = oracle.lib()
     t1, t2 = _which_threshold(oracle, 2), _which_threshold(oracle, 3)
     assert 0 < t1 < t2 < 2**32

@@ -1,7 +1,7 @@
 // bvh_walk_sim.cpp -- CPU walk statistics of sphere-BVH layouts on the C3
 // scene (development tool: which layout fits the LDS and what a walk costs).
 //
-// Builds the host's binned-SAH tree (rtp_host.cpp bvh_build: 16 bins, the
+// Builds the host's binned-SAH tree (rtp_bvh_host.hpp bvh_build: 16 bins, the
 // same sphere-box pad) for a leaf-size bound, then walks random rays from
 // points inside the room (outside every sphere), bounded by the walls, with
 //   threaded: the 8 octant-ordered threaded copies (bvh_flatten, top-box drop

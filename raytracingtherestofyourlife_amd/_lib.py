@@ -1,4 +1,8 @@
-"""ctypes binding of librtp.so (include/rtp.h).
+"""ctypes binding of librtp.so: the one table of its C signatures (SIGNATURES,
+a group of rows per header: include/rtp.h, rtp_mesh.h, rtp_adaptive.h, and the
+internal hooks), the one place that applies it (bind, which load() calls; a
+tool binds its A/B library with it too), the structs and the pointer helpers.
+A new entry point is a row in its header's group, in the header's order.
 
 There is no CPU fallback: if the HIP library is missing or fails to load,
 every entry point raises.  The product path is the HIP path.
@@ -73,6 +77,11 @@ class RtpDenoiseParams(ctypes.Structure):
                 ("sigma_a", ctypes.c_float), ("normal_log2", ctypes.c_int32)]
 
 
+class RtpRefineParams(ctypes.Structure):
+    """rtp_refine_params (include/rtp_adaptive.h)."""
+    _fields_ = [("threshold", ctypes.c_float), ("spp", ctypes.c_int32), ("max_spp", ctypes.c_int32)]
+
+
 RTP_AOV_COLOR, RTP_AOV_NORMALS, RTP_AOV_ALBEDO = 1, 2, 4
 RTP_FF_TABLES_AUTO, RTP_FF_TABLES_OFF, RTP_FF_TABLES_ON = 0, 1, 2
 
@@ -97,18 +106,28 @@ DEBUG_COUNTERS = ("bounce_steps", "bounce_lanes", "ff_phases", "ff_lanes", "ff_i
 N_DBG_COUNTERS = len(DEBUG_COUNTERS) - 1  # rtp::kDbgCounters: the width of a per-wave record
 
 
+# The internal hooks that Python code of this repository calls (the package's
+# mesh helpers, the tests, the tools): exported beside the public entry points
+# and declared, for the C++ units, in these two headers of csrc/.
+HOOKS = "hooks"
+HOOK_HEADERS = ("rtp_launch_decl.hpp", "rtp_mesh.hpp")
+
+
 def _signatures() -> dict:
-    """Every function of include/rtp.h, in its order: name -> (restype, argtypes)."""
+    """Every function Python calls in librtp.so, grouped by the header that
+    declares it and in that header's order: group -> name -> (restype, argtypes)."""
     i32, u32, i64, st = ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int32  # st: rtp_status
     P = ctypes.POINTER
     u64p, d64p = P(ctypes.c_uint64), P(ctypes.c_double)
     cam, stats, aux, state = P(RtpCamera), P(RtpStats), P(RtpPixelAux), P(RtpRenderState)
-    return {
+    desc, prm = P(RtpSceneDesc), P(RtpRefineParams)
+    cint, cintp = ctypes.c_int, P(ctypes.c_int)  # the launcher header's plain C types
+    return {"include/rtp.h": {
         "rtp_last_error": (ctypes.c_char_p, []),
         "rtp_abi_version": (i32, []),
         "rtp_create": (st, [i32, P(vp)]),
         "rtp_destroy": (None, [vp]),
-        "rtp_set_scene": (st, [vp, P(RtpSceneDesc)]),
+        "rtp_set_scene": (st, [vp, desc]),
         "rtp_render": (st, [vp, cam, i32, i32, i32, i32, u32, f32p, stats]),
         "rtp_render_tiles_device": (st, [vp, cam, i32, i32, i32, i32, u32, i32, i32, vp, vp, stats]),
         "rtp_render_device": (st, [vp, cam, i32, i32, i32, i32, u32, i64, i64, vp, vp, aux, vp, stats]),
@@ -127,7 +146,7 @@ def _signatures() -> dict:
         "rtp_denoise": (st, [vp, f32p, f32p, f32p, i32, i32, P(RtpDenoiseParams), f32p, stats]),
         "rtp_normalize": (st, [f32p, i64, i32]),
         "rtp_write_pnm": (st, [ctypes.c_char_p, f32p, i32, i32]),
-        "rtp_cornell_box": (st, [i32, P(RtpSceneDesc)]),
+        "rtp_cornell_box": (st, [i32, desc]),
         "rtp_render_direct": (st, [vp, cam, i32, i32, P(RtpDirectDesc), f32p, f32p, f32p, f32p, stats]),
         "rtp_render_direct_device": (st, [vp, cam, i32, i32, P(RtpDirectDesc), vp, vp, vp, vp, vp, stats]),
         "rtp_sample_color_table": (st, [d64p, i32, d64p, i32, d64p, i32, f32p]),
@@ -145,22 +164,51 @@ def _signatures() -> dict:
         "rtp_sphere_walk": (i32, [vp]),
         "rtp_sphere_walk_oct_mask": (i32, [vp]),
         "rtp_verify_fast_math": (st, [vp, i32, u32, u32, u64p, P(u32)]),
-    }
+    }, "include/rtp_mesh.h": {
+        "rtp_set_scene_mesh": (st, [vp, desc]),
+        "rtp_mesh_guarantee": (st, [vp, f32p, f32p]),
+        "rtp_mesh_counts": (st, [vp, i32p, i32p, i32p]),
+        "rtp_set_scene_mesh_device": (st, [vp, desc, vp]),
+    }, "include/rtp_adaptive.h": {
+        "rtp_noise_device": (st, [vp, vp, vp, vp, i64, vp, vp, stats]),
+        "rtp_noise": (st, [vp, f32p, f32p, i32p, i64, f32p, stats]),
+        "rtp_select_active_device": (st, [vp, vp, vp, vp, i64, prm, vp, vp, vp, stats]),
+        "rtp_refine_device": (st, [vp, cam, i32, i32, i32, state, vp, prm, i64p, vp, stats]),
+        "rtp_refine": (st, [vp, cam, i32, i32, i32, state, i32p, prm, i64p, stats]),
+        "rtp_render_adaptive_device": (st, [vp, cam, i32, i32, i32, state, vp, prm, i32, i64p, P(i32), vp, stats]),
+        "rtp_refine_last_timing": (st, [vp, d64p]),
+        "rtp_normalize_counts": (st, [f32p, i32p, i64]),
+    }, HOOKS: {
+        # csrc/rtp_launch_decl.hpp
+        "rtp_instance_name": (ctypes.c_char_p, [cint] * 8),
+        "rtp_plan_history_lanes": (i64, [i64, cint, cint, cint, cintp, cintp]),
+        "rtp_plan_steal": (cint, [i64, cint]),
+        # csrc/rtp_mesh.hpp
+        "rtp_mesh_build_host": (st, [desc, i32, i32, i32p, vp, i32p, f32p, f32p, f32p]),
+        "rtp_mesh_leaf_size": (i32, []),
+        "rtp_mesh_compact_host": (None, [vp, i64, u32p]),
+        "rtp_mesh_scan_host": (st, [desc, f32p, i64, u32p]),
+        "rtp_debug_mesh_readback": (st, [vp, i32, i32, i32p, vp, i32p, f32p, f32p]),
+        "rtp_debug_mesh_records": (st, [vp, i64, vp]),
+    }}
 
 
 SIGNATURES = _signatures()
-EXPORTED_SYMBOLS = list(SIGNATURES)
-# include/rtp_mesh.h (mesh scenes), bound by load() with the table above
-MESH_SIGNATURES = {
-    "rtp_set_scene_mesh": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc)]),
-    "rtp_mesh_guarantee": (ctypes.c_int32, [vp, f32p, f32p]),
-    "rtp_set_scene_mesh_device": (ctypes.c_int32, [vp, ctypes.POINTER(RtpSceneDesc), vp]),
-}
-# include/rtp_mesh.h, triangle cells: the later additions in a table of their
-# own (MESH_SIGNATURES is the mesh scenes' first three), bound by load() too
-MESH_TRI_SIGNATURES = {
-    "rtp_mesh_counts": (ctypes.c_int32, [vp, i32p, i32p, i32p]),
-}
+EXPORTED_SYMBOLS = list(SIGNATURES["include/rtp.h"])
+
+
+def bind(L: ctypes.CDLL) -> list:
+    """Apply every row of SIGNATURES to L: the names L does not export."""
+    missing = []
+    for group in SIGNATURES.values():
+        for name, (restype, argtypes) in group.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                missing.append(name)
+                continue
+            fn.restype, fn.argtypes = restype, argtypes
+    return missing
 
 
 class RtpError(RuntimeError):
@@ -199,14 +247,7 @@ def load(build_if_missing: bool = True) -> ctypes.CDLL:
     # before any of the symbols (tools/build_variant.sh RTP_SRC_REV, the A/B
     # baselines of the tools/*_bench.py): it loads without them, and calling
     # one raises AttributeError.  The in-tree library must export them all.
-    missing = []
-    for name, (restype, argtypes) in {**SIGNATURES, **MESH_SIGNATURES, **MESH_TRI_SIGNATURES}.items():
-        try:
-            fn = getattr(L, name)
-        except AttributeError:
-            missing.append(name)
-            continue
-        fn.restype, fn.argtypes = restype, argtypes
+    missing = bind(L)
     if missing and not os.environ.get("RTP_LIB_PATH"):
         raise RuntimeError(f"{LIB_PATH} does not export {', '.join(missing)}; rebuild it "
                            "(raytracingtherestofyourlife_amd/build.py)")

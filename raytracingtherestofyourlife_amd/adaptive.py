@@ -1,11 +1,11 @@
-"""Adaptive sampling on the device: the ctypes table of include/rtp_adaptive.h
-and its entry points as functions of a Device.
+"""Adaptive sampling on the device: the entry points of include/rtp_adaptive.h
+as functions of a Device.
 
-The table is applied to the library _lib.load() returns on first use, so a
-library without these symbols (an experiment's RTP_LIB_PATH baseline) still
-loads; calling one of them then raises.  Each function is one entry point:
-its argument checks, its output buffers and its argument order, like
-Device's methods.
+Each function is one entry point: its argument checks, its output buffers and
+its argument order, like Device's methods, over the same marshalling: _lib's
+table (the rows of include/rtp_adaptive.h) and Device._call.  A library
+without these symbols (an experiment's RTP_LIB_PATH baseline) still loads;
+calling one of them then raises AttributeError.
 """
 from __future__ import annotations
 
@@ -14,8 +14,7 @@ from typing import TYPE_CHECKING
 
 import numpy as np
 
-from . import _lib
-from ._lib import ErrorBadValue, RtpCamera, RtpRenderState, RtpStats, check, f32p, i32p, i64p, ptr, render_state, vp
+from ._lib import ErrorBadValue, RtpRefineParams, RtpStats, check, load, ptr, render_state
 
 if TYPE_CHECKING:
     from .device import Device
@@ -23,50 +22,6 @@ if TYPE_CHECKING:
 
 SELECT_BLOCK = 2048  # entries per block of the selection (csrc/rtp_adaptive.hpp kSelBlock)
 SCAN_THREADS = 256   # block counts the scan takes per chunk (kScanThreads)
-
-
-class RtpRefineParams(ctypes.Structure):
-    _fields_ = [("threshold", ctypes.c_float), ("spp", ctypes.c_int32), ("max_spp", ctypes.c_int32)]
-
-
-def _signatures() -> dict:
-    """Every function of include/rtp_adaptive.h, in its order: name -> (restype, argtypes)."""
-    i32, i64, st = ctypes.c_int32, ctypes.c_int64, ctypes.c_int32  # st: rtp_status
-    P = ctypes.POINTER
-    cam, stats, state, prm = P(RtpCamera), P(RtpStats), P(RtpRenderState), P(RtpRefineParams)
-    return {
-        "rtp_noise_device": (st, [vp, vp, vp, vp, i64, vp, vp, stats]),
-        "rtp_noise": (st, [vp, f32p, f32p, i32p, i64, f32p, stats]),
-        "rtp_select_active_device": (st, [vp, vp, vp, vp, i64, prm, vp, vp, vp, stats]),
-        "rtp_refine_device": (st, [vp, cam, i32, i32, i32, state, vp, prm, i64p, vp, stats]),
-        "rtp_refine": (st, [vp, cam, i32, i32, i32, state, i32p, prm, i64p, stats]),
-        "rtp_render_adaptive_device": (st, [vp, cam, i32, i32, i32, state, vp, prm, i32, i64p, P(i32), vp, stats]),
-        "rtp_refine_last_timing": (st, [vp, P(ctypes.c_double)]),
-        "rtp_normalize_counts": (st, [f32p, i32p, i64]),
-    }
-
-
-SIGNATURES = _signatures()
-_applied_to = None
-
-
-def lib() -> ctypes.CDLL:
-    """_lib.load() with this module's table applied (once per library)."""
-    global _applied_to
-    L = _lib.load()
-    if _applied_to is not L:
-        for name, (restype, argtypes) in SIGNATURES.items():
-            fn = getattr(L, name)  # AttributeError: a library from before these entry points
-            fn.restype, fn.argtypes = restype, argtypes
-        _applied_to = L
-    return L
-
-
-def _call(dev: "Device", entry: str, *args, stats: bool = True) -> RtpStats:
-    """Device._call over this module's table."""
-    st = RtpStats()
-    check(getattr(lib(), entry)(dev.handle, *args, st if stats else None))
-    return st
 
 
 def refine_params(spp: int, threshold: float, max_spp: int) -> RtpRefineParams:
@@ -78,7 +33,7 @@ def noise_device(dev: "Device", sums_ptr: int, m2_ptr: int, count_ptr: int, n: i
     """rtp_noise_device: the noise estimate of a device-resident render state
     (sums_ptr float4[n], m2_ptr float[n], count_ptr int32[n]) into noise_ptr
     float[n].  Asynchronous unless timed."""
-    return _call(dev, "rtp_noise_device", sums_ptr, m2_ptr, count_ptr, int(n), noise_ptr, stream, stats=timed)
+    return dev._call("rtp_noise_device", sums_ptr, m2_ptr, count_ptr, int(n), noise_ptr, stream, stats=timed)
 
 
 def noise(dev: "Device", sums: np.ndarray, m2: np.ndarray, count: np.ndarray) -> np.ndarray:
@@ -87,7 +42,7 @@ def noise(dev: "Device", sums: np.ndarray, m2: np.ndarray, count: np.ndarray) ->
     n = sums.shape[0]
     _expect("noise", [(sums, np.float32, (n, 4)), (m2, np.float32, (n,)), (count, np.int32, (n,))])
     out = np.zeros(n, dtype=np.float32)
-    _call(dev, "rtp_noise", ptr(sums), ptr(m2), ptr(count), n, ptr(out))
+    dev._call("rtp_noise", ptr(sums), ptr(m2), ptr(count), n, ptr(out))
     return out
 
 
@@ -97,8 +52,8 @@ def select_active_device(dev: "Device", sums_ptr: int, m2_ptr: int, count_ptr: i
     """rtp_select_active_device: the active entries' ids, ascending, into
     ids_ptr (device int64[n]) and their number into n_selected_ptr (device
     int64).  Asynchronous unless timed."""
-    return _call(dev, "rtp_select_active_device", sums_ptr, m2_ptr, count_ptr, int(n),
-                 refine_params(spp, threshold, max_spp), ids_ptr, n_selected_ptr, stream, stats=timed)
+    return dev._call("rtp_select_active_device", sums_ptr, m2_ptr, count_ptr, int(n),
+                     refine_params(spp, threshold, max_spp), ids_ptr, n_selected_ptr, stream, stats=timed)
 
 
 def refine_device(dev: "Device", camera: "Camera", nx: int, ny: int, depth: int, rgba_ptr: int, seed_ptr: int,
@@ -109,9 +64,9 @@ def refine_device(dev: "Device", camera: "Camera", nx: int, ny: int, depth: int,
     for the selection's total; the pass's launches are queued, not waited for
     (unless timed)."""
     total = ctypes.c_int64(-1)
-    st = _call(dev, "rtp_refine_device", camera.to_c() if camera is not None else None, nx, ny, depth,
-               render_state(rgba_ptr, seed_ptr, live_ptr, m2_ptr), count_ptr, refine_params(spp, threshold, max_spp),
-               total, stream, stats=timed)
+    st = dev._call("rtp_refine_device", camera.to_c() if camera is not None else None, nx, ny, depth,
+                   render_state(rgba_ptr, seed_ptr, live_ptr, m2_ptr), count_ptr,
+                   refine_params(spp, threshold, max_spp), total, stream, stats=timed)
     return int(total.value), st
 
 
@@ -129,8 +84,8 @@ def refine(dev: "Device", camera: "Camera", nx: int, ny: int, depth: int, rgba: 
     if n != int(nx) * int(ny):
         raise ErrorBadValue(f"refine: a state of {n} entries for a {nx} x {ny} canvas")
     total = ctypes.c_int64(-1)
-    _call(dev, "rtp_refine", camera.to_c(), nx, ny, depth, render_state(rgba, seed, live, m2), ptr(count),
-          refine_params(spp, threshold, max_spp), total)
+    dev._call("rtp_refine", camera.to_c(), nx, ny, depth, render_state(rgba, seed, live, m2), ptr(count),
+              refine_params(spp, threshold, max_spp), total)
     return int(total.value)
 
 
@@ -143,16 +98,16 @@ def render_adaptive_device(dev: "Device", camera: "Camera", nx: int, ny: int, de
         raise ErrorBadValue("render_adaptive_device: max_passes must be >= 1")
     per_pass = np.full(int(max_passes), -1, dtype=np.int64)
     run = ctypes.c_int32(0)
-    _call(dev, "rtp_render_adaptive_device", camera.to_c(), nx, ny, depth,
-          render_state(rgba_ptr, seed_ptr, live_ptr, m2_ptr), count_ptr, refine_params(spp, threshold, max_spp),
-          int(max_passes), ptr(per_pass), run, stream, stats=False)
+    dev._call("rtp_render_adaptive_device", camera.to_c(), nx, ny, depth,
+              render_state(rgba_ptr, seed_ptr, live_ptr, m2_ptr), count_ptr, refine_params(spp, threshold, max_spp),
+              int(max_passes), ptr(per_pass), run, stream, stats=False)
     return [int(v) for v in per_pass[: run.value]]
 
 
 def refine_last_timing(dev: "Device") -> dict:
     """The device times (ms) of the parts of the last timed refine_device."""
     ms = (ctypes.c_double * 4)()
-    check(lib().rtp_refine_last_timing(dev.handle, ms))
+    check(dev._L.rtp_refine_last_timing(dev.handle, ms))
     return dict(select=ms[0], gather=ms[1], resume=ms[2], scatter=ms[3])
 
 
@@ -163,7 +118,7 @@ def normalize_counts(rgba_sum: np.ndarray, count: np.ndarray) -> np.ndarray:
     c = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
     if c.size != a.shape[0]:
         raise ErrorBadValue(f"normalize_counts: {c.size} counts for {a.shape[0]} pixels")
-    check(lib().rtp_normalize_counts(ptr(a), ptr(c), a.shape[0]))
+    check(load().rtp_normalize_counts(ptr(a), ptr(c), a.shape[0]))
     return a
 
 

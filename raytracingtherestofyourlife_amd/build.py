@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "librtp.so")
 DEVICE_FREE_SOURCES = ["rtp_base_host.cpp", "rtp_scene_host.cpp", "rtp_mesh_host.cpp", "scene_cornell.cpp"]
 SOURCES = ["rtp_kernels.hip", "rtp_direct.hip", "rtp_bvh_gpu.hip", "rtp_mesh_gpu.hip", "rtp_denoise.hip", "rtp_adaptive.hip", "rtp_host.cpp", "rtp_ff_host.cpp", "rtp_debug_host.cpp", "rtp_direct_host.cpp", "rtp_adaptive_host.cpp",
            *DEVICE_FREE_SOURCES]
-HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_base.hpp", "rtp_host_util.hpp", "rtp_scene.hpp", "rtp_ff.hpp", "rtp_adaptive.hpp", "rtp_bvh_host.hpp", "rtp_mesh.hpp", "rtp_mesh_gpu.hpp", "rtp_mesh_cell.hpp", "rtp_lbvh.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
+HEADERS = ["rtp_trace.hpp", "rtp_pool.hpp", "rtp_diag.hpp", "rtp_launch.hpp", "rtp_launch_decl.hpp", "rtp_device.hpp", "rtp_layout.hpp", "rtp_context.hpp", "rtp_host_base.hpp", "rtp_host_util.hpp", "rtp_scene.hpp", "rtp_ff.hpp", "rtp_adaptive.hpp", "rtp_bvh_host.hpp", "rtp_mesh.hpp", "rtp_mesh_gpu.hpp", "rtp_mesh_cell.hpp", "rtp_lbvh.hpp", "glibc_powf.hpp", os.path.join("..", "..", "include", "rtp.h"),
            os.path.join("..", "..", "include", "rtp_adaptive.h"), os.path.join("..", "..", "include", "rtp_mesh.h")]
 ARCH = os.environ.get("RTP_OFFLOAD_ARCH", "gfx950")
 

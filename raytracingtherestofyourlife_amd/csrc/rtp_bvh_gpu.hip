@@ -24,6 +24,7 @@
 
 #include <hipcub/hipcub.hpp>
 
+#include "rtp_launch_decl.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_lbvh.hpp"
 #include "rtp_mesh_cell.hpp"

@@ -12,20 +12,10 @@
 #include "rtp_context.hpp"
 #include "rtp_ff.hpp"
 #include "rtp_host_util.hpp"
+#include "rtp_launch_decl.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_mesh.hpp"
 #include "rtp_scene.hpp"
-
-extern "C" hipError_t rtp_launch_eval_primitive(int kind, const void* in, void* out, int64_t n, const uint32_t* tab,
-                                                uint32_t t1, uint32_t t2, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_closest(const rtp::DevScene* scene, const float* rays, uint32_t* out,
-                                              int64_t n, int bvh, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_bounce(const rtp::DevScene* scene, const float* rays, const uint32_t* seeds,
-                                             uint32_t* out, int64_t n, int bvh, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_raygen(const rtp::DevCamera* cam, int nx, int ny, const int64_t* pixels,
-                                             const uint32_t* seeds, uint32_t* out, int64_t n, hipStream_t stream);
-extern "C" hipError_t rtp_launch_verify_fast_math(int kind, uint32_t lo, uint64_t count, unsigned long long* bad,
-                                                  uint32_t* first_bad, hipStream_t stream);
 
 using namespace rtp_host;
 

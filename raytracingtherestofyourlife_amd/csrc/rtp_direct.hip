@@ -17,6 +17,7 @@
 
 #include "glibc_powf.hpp"
 #include "rtp_device.hpp"
+#include "rtp_launch_decl.hpp"
 
 namespace rtp {
 

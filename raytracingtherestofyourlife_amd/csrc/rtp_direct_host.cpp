@@ -23,10 +23,8 @@
 #include "../../include/rtp.h"
 #include "rtp_context.hpp"
 #include "rtp_host_util.hpp"
+#include "rtp_launch_decl.hpp"
 #include "rtp_layout.hpp"
-
-extern "C" hipError_t rtp_launch_direct(const rtp::DevScene* scene, const rtp::DirectParams* p, hipStream_t stream);
-extern "C" hipError_t rtp_launch_eval_powf(const float* x, float y, float* out, int64_t n, hipStream_t stream);
 
 using namespace rtp_host;
 

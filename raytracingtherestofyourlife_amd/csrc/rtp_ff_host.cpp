@@ -13,11 +13,9 @@
 #include "rtp_context.hpp"
 #include "rtp_ff.hpp"
 #include "rtp_host_util.hpp"
+#include "rtp_launch_decl.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_scene.hpp"
-
-extern "C" hipError_t rtp_launch_build_ff_tables(const rtp::FfBuildOut* out, int max_r, uint32_t t1, uint32_t t2,
-                                                 hipStream_t stream);
 
 namespace rtp_host {
 

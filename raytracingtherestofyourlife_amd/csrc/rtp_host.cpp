@@ -21,24 +21,11 @@
 #include "rtp_context.hpp"
 #include "rtp_ff.hpp"
 #include "rtp_host_util.hpp"
+#include "rtp_launch_decl.hpp"
 #include "rtp_layout.hpp"
 #include "rtp_mesh.hpp"
 #include "rtp_mesh_gpu.hpp"
 #include "rtp_scene.hpp"
-
-extern "C" const char* rtp_instance_name(int variant, int stats, int walk, int tiles, int plan, int steal, int views,
-                                         int resume);
-extern "C" int64_t rtp_plan_history_lanes(int64_t npix, int spp, int bvh, int stats, int* variant_out, int* waves_out);
-extern "C" int rtp_plan_steal(int64_t npix, int bvh);
-extern "C" hipError_t rtp_launch_render(const rtp::DevScene* scene, const rtp::KParams* p, int variant, int waves, int bvh,
-                                        int stats, int steal, hipStream_t stream, int lds_bytes);
-extern "C" int rtp_lds_walk_capacity(void);
-extern "C" hipError_t rtp_compact_bvh(const rtp::BvhNode* d_nodes, int64_t total, uint32_t* d_cn, int32_t* d_cidx,
-                                      hipStream_t stream);
-extern "C" hipError_t rtp_build_bvh_gpu(const float4* d_cr, int n, float3 lo, float3 ext, float reach,
-                                        rtp::BvhNode* d_nodes, rtp::DevSphereG* d_geom, hipStream_t stream);
-extern "C" hipError_t rtp_launch_guides(const rtp::DevScene* scene, const rtp::GuideParams* p, int bvh,
-                                        hipStream_t stream);
 
 using namespace rtp_host;
 

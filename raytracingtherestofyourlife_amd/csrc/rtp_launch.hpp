@@ -1,12 +1,13 @@
 // rtp_launch.hpp -- the host side of rtp_kernels.hip: the table of
 // render-kernel instances, the occupancy planning over it, and the launchers
-// (extern "C", declared by hand in rtp_host.cpp; none is part of rtp.h).
+// (extern "C", declared in rtp_launch_decl.hpp; none is part of rtp.h).
 #pragma once
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
 #include "rtp_diag.hpp"
+#include "rtp_launch_decl.hpp"
 #include "rtp_pool.hpp"
 
 namespace {

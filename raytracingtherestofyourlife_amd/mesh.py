@@ -119,12 +119,9 @@ def mesh_pads(coords, cells, sphere_points=(), sphere_radius=()):
     none = np.zeros(len(sp), np.int32)
     desc, keep = scene_desc(pts, rows, zeros, zeros, sp, sr, none, none, [0], [0], np.zeros((1, 3), np.float32),
                             (int(sp[0]),) * 4, int(sp[0]), 1.5)
-    L = _lib.load()
-    fn = L.rtp_mesh_build_host
-    fn.restype = ctypes.c_int32
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p] + [ctypes.c_void_p] * 5
     pads = np.zeros(n, dtype=np.float32)
-    _lib.check(fn(ctypes.addressof(desc), 0, 0, None, None, None, None, pads.ctypes.data, None))
+    # (byref: what both a typed and a void* parameter take, should a caller have retyped the shared library's hook)
+    _lib.check(_lib.load().rtp_mesh_build_host(ctypes.byref(desc), 0, 0, None, None, None, None, _lib.ptr(pads), None))
     del keep
     return pads
 

@@ -360,9 +360,7 @@ def build_host(m, oct=0):
     """rtp_mesh_build_host: dict(nodes, order, boxes, pads, cos_min, reach)."""
     import raytracingtherestofyourlife_amd as rtp
 
-    L = rtp.load()
-    L.rtp_mesh_build_host.restype = ctypes.c_int32
-    L.rtp_mesh_build_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p] + [ctypes.c_void_p] * 5
+    L, ptr = rtp.load(), rtp._lib.ptr
     desc, keep = m.desc()
     nq = len(m.quads)
     nodes = np.zeros(2 * nq, dtype=NODE)
@@ -371,8 +369,7 @@ def build_host(m, oct=0):
     pads = np.zeros(nq, dtype=F)
     g = np.zeros(2, dtype=F)
     nn = ctypes.c_int32(0)
-    rc = L.rtp_mesh_build_host(ctypes.addressof(desc), oct, len(nodes), ctypes.addressof(nn), nodes.ctypes.data,
-                               order.ctypes.data, boxes.ctypes.data, pads.ctypes.data, g.ctypes.data)
+    rc = L.rtp_mesh_build_host(desc, oct, len(nodes), nn, nodes.ctypes.data, ptr(order), ptr(boxes), ptr(pads), ptr(g))
     assert rc == 0, L.rtp_last_error()
     del keep
     return dict(nodes=nodes[: nn.value], order=order, boxes=boxes, pads=pads, cos_min=float(g[0]), reach=float(g[1]))
@@ -383,10 +380,7 @@ def host_scan(m, ray, threads=8):
     """rtp_mesh_scan_host over the rays in parallel slices: (t bits uint32 [n],
     winner int32 [n], -1: no quad)."""
     import raytracingtherestofyourlife_amd as rtp
-    L = rtp.load()
-    fn = L.rtp_mesh_scan_host
-    fn.restype = ctypes.c_int32
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
+    fn, ptr = rtp.load().rtp_mesh_scan_host, rtp._lib.ptr
     desc, keep = m.desc()
     ray = np.ascontiguousarray(ray, dtype=F)
     out = np.zeros((len(ray), 2), dtype=np.uint32)
@@ -394,7 +388,7 @@ def host_scan(m, ray, threads=8):
 
     def run(k):
         a, b = cuts[k], cuts[k + 1]
-        return fn(ctypes.addressof(desc), ray[a:b].ctypes.data, b - a, out[a:b].ctypes.data)
+        return fn(desc, ptr(ray[a:b]), b - a, ptr(out[a:b]))
 
     with ThreadPoolExecutor(threads) as ex:
         assert all(rc == 0 for rc in ex.map(run, range(threads)))

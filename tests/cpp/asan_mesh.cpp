@@ -14,11 +14,7 @@
 #include <vector>
 
 #include "rtp.h"
-
-extern "C" rtp_status rtp_mesh_build_host(const rtp_scene_desc* scene, int32_t oct, int32_t node_cap, int32_t* n_nodes,
-                                          void* nodes, int32_t* order, float* boxes, float* pads, float* guarantee);
-extern "C" rtp_status rtp_mesh_scan_host(const rtp_scene_desc* s, const float* rays, int64_t n, uint32_t* out);
-extern "C" int32_t rtp_mesh_leaf_size(void);
+#include "rtp_mesh.hpp"
 
 static int failures = 0;
 #define EXPECT(cond)                                               \

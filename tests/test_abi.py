@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -30,75 +32,47 @@ def test_library_exports_every_declared_symbol():
     out = subprocess.run(["nm", "-D", "--defined-only", rtp.LIB_PATH], capture_output=True, text=True).stdout
     for n in names:
         assert re.search(rf"\bT {n}$", out, flags=re.M), n
-    assert set(names) == set(rtp._lib.EXPORTED_SYMBOLS)
+    assert set(names) == set(rtp._lib.EXPORTED_SYMBOLS) == set(rtp._lib.SIGNATURES["include/rtp.h"])
 
 
-def _prototypes():
-    """include/rtp.h's functions: name -> (return type, [argument declarations])."""
-    src = open(os.path.join(ROOT, "include", "rtp.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(rtp_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        args = [a.strip() for a in args.split(",")]
-        protos[name] = (" ".join(ret.split()), [] if args == ["void"] else args)
-    return protos
-
-
-def _c_class(decl: str):
-    """(base type, pointer depth) of a C argument declaration `type name` or `type name[n]`."""
-    ctype, array = re.fullmatch(r"(.*?)\b\w+\s*(\[\d*\])?", decl).groups()
-    words = [w for w in ctype.replace("*", " ").split() if w != "const"]
-    return words[0], ctype.count("*") + (1 if array else 0)
-
-
-def _agrees(ct, base: str, depth: int) -> bool:
-    """The ctypes type `ct` against a C declaration of `base` with `depth` stars."""
+@pytest.mark.parametrize("group", [*_abi.PUBLIC_HEADERS, "hooks"])
+def test_signature_table_matches_the_header(group):
+    """Every row of a group of _lib.SIGNATURES against its prototype: argument
+    count, each argument's class (exact scalar; pointer kind and pointee; a
+    struct pointer typed, never void*), return class.  A public header's group
+    is the header: the same names in the same order.  The hooks' group holds
+    what Python calls of csrc/rtp_launch_decl.hpp and csrc/rtp_mesh.hpp, in
+    their order; launchers that take device structs have no row."""
     from raytracingtherestofyourlife_amd import _lib
 
-    scalars = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
-               "uint64_t": ctypes.c_uint64, "float": ctypes.c_float, "double": ctypes.c_double}
-    structs = {"rtp_camera": _lib.RtpCamera, "rtp_view": _lib.RtpView, "rtp_scene_desc": _lib.RtpSceneDesc,
-               "rtp_stats": _lib.RtpStats, "rtp_pixel_aux": _lib.RtpPixelAux, "rtp_render_state": _lib.RtpRenderState,
-               "rtp_direct_desc": _lib.RtpDirectDesc, "rtp_denoise_params": _lib.RtpDenoiseParams,
-               "rtp_ff_info": _lib.RtpFfInfo}
-    if depth == 0:
-        return base in ("int32_t", "uint32_t", "int64_t", "float") and ct is scalars[base]
-    if ct is ctypes.c_void_p:
-        return True
-    if ct is ctypes.c_char_p:
-        return base == "char" and depth == 1
-    if isinstance(ct, type) and issubclass(ct, ctypes._Pointer):
-        if depth > 1:
-            return _agrees(ct._type_, base, depth - 1)
-        # the pointee the header names; rtp_context and void have no mirror and must be c_void_p
-        return ct._type_ is {**scalars, **structs}.get(base)
-    return False
-
-
-def test_signature_table_matches_the_header():
-    """Every row of _lib.SIGNATURES against its prototype: argument count,
-    each argument's class (exact scalar; pointer kind and pointee), return class."""
-    from raytracingtherestofyourlife_amd import _lib
-
-    protos = _prototypes()
-    assert set(protos) == set(_lib.SIGNATURES) and len(protos) == 40
-    assert list(protos) == list(_lib.SIGNATURES), "the table is in the header's order"
-    returns = {"rtp_status": ctypes.c_int32, "int32_t": ctypes.c_int32, "const char*": ctypes.c_char_p, "void": None}
-    bad = []
-    for name, (ret, args) in protos.items():
-        restype, argtypes = _lib.SIGNATURES[name]
-        if restype is not returns[ret]:
-            bad.append(f"{name}: returns {ret}, table {restype}")
-        if len(argtypes) != len(args):
-            bad.append(f"{name}: {len(args)} arguments, table {len(argtypes)}")
-            continue
-        bad += [f"{name}: argument {k} `{decl}`, table {ct}" for k, (decl, ct) in enumerate(zip(args, argtypes))
-                if not _agrees(ct, *_c_class(decl))]
+    rows = _lib.SIGNATURES[group]
+    if group in _abi.PUBLIC_HEADERS:
+        protos = _abi.prototypes(group)
+        assert set(protos) == set(rows) and len(protos) == _abi.PUBLIC_HEADERS[group]
+        assert list(protos) == list(rows), "the table is in the header's order"
+    else:
+        assert group == _lib.HOOKS and list(_lib.SIGNATURES) == [*_abi.PUBLIC_HEADERS, _lib.HOOKS]
+        protos = _abi.prototypes(*[os.path.relpath(os.path.join(_abi.CSRC, h), ROOT) for h in _lib.HOOK_HEADERS])
+        assert rows and not set(rows) - set(protos), "every hook row has a prototype"
+        assert [n for n in protos if n in rows] == list(rows), "the rows are in the headers' order"
+    bad = _abi.disagreements(protos, rows, plain_c=group == _lib.HOOKS)
     assert not bad, "\n".join(bad)
-    # and load() applied the table
+    # no name in two groups
+    assert all(name not in g for key, g in _lib.SIGNATURES.items() if key != group for name in rows)
+    # and load() applied the rows
     L = _lib.load()
-    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+    for name, (restype, argtypes) in rows.items():
         assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+
+
+def test_refine_params_mirror_the_header():
+    from raytracingtherestofyourlife_amd import _lib
+
+    fields = [(n, t) for n, t in _lib.RtpRefineParams._fields_]
+    assert fields == [("threshold", ctypes.c_float), ("spp", ctypes.c_int32), ("max_spp", ctypes.c_int32)]
+    body = re.search(r"typedef struct \{(.*?)\} rtp_refine_params;", _abi.source("include/rtp_adaptive.h"),
+                     flags=re.S).group(1)
+    assert re.findall(r"(\w+)\s+(\w+);", body) == [("float", "threshold"), ("int32_t", "spp"), ("int32_t", "max_spp")]
 
 
 def test_load_missing_symbol_rule(tmp_path, monkeypatch):
@@ -106,7 +80,7 @@ def test_load_missing_symbol_rule(tmp_path, monkeypatch):
     AttributeError); the in-tree library must export them all."""
     import raytracingtherestofyourlife_amd._lib as L
 
-    src, stub = tmp_path / "stub.c", str(tmp_path / "libstub.so")
+    src, stub, stub2 = tmp_path / "stub.c", str(tmp_path / "libstub.so"), str(tmp_path / "libstub2.so")
     src.write_text('const char* rtp_last_error(void) { return ""; }\nint rtp_abi_version(void) { return 3; }\n')
     subprocess.run([os.environ.get("CC", "cc"), "-shared", "-fPIC", str(src), "-o", stub], check=True,
                    capture_output=True)
@@ -120,6 +94,24 @@ def test_load_missing_symbol_rule(tmp_path, monkeypatch):
     monkeypatch.setattr(L, "_lib", None)
     monkeypatch.delenv("RTP_LIB_PATH")
     with pytest.raises(RuntimeError, match="rtp_render_views"):
+        L.load(build_if_missing=False)
+    assert L._lib is None
+    # the same rule for the rows beyond rtp.h: a stub with every public entry point but no
+    # adaptive one and no internal hook
+    public = [n for g in ("include/rtp.h", "include/rtp_mesh.h") for n in L.SIGNATURES[g]]
+    src.write_text("".join(f"int {n}(void) {{ return 3; }}\n" for n in public))
+    subprocess.run([os.environ.get("CC", "cc"), "-shared", "-fPIC", str(src), "-o", stub2], check=True,
+                   capture_output=True)
+    monkeypatch.setattr(L, "LIB_PATH", stub2)
+    monkeypatch.setenv("RTP_LIB_PATH", stub2)
+    lib = L.load(build_if_missing=False)
+    assert lib.rtp_abi_version() == 3
+    for name in ("rtp_refine_device", "rtp_plan_steal"):
+        with pytest.raises(AttributeError):
+            getattr(lib, name)
+    monkeypatch.setattr(L, "_lib", None)
+    monkeypatch.delenv("RTP_LIB_PATH")
+    with pytest.raises(RuntimeError, match="rtp_noise_device.*rtp_plan_steal"):
         L.load(build_if_missing=False)
     assert L._lib is None
 

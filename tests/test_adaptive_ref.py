@@ -1,5 +1,5 @@
-"""Adaptive sampling without a GPU: include/rtp_adaptive.h against the ctypes
-table of raytracingtherestofyourlife_amd.adaptive and librtp.so's exports; the
+"""Adaptive sampling without a GPU: include/rtp_adaptive.h against librtp.so's
+exports (tests/test_abi.py holds its rows of the ctypes table to it); the
 float32 restatement of the noise estimate and the selection
 (tests/_adaptive_ref.py) against the package's float64 rule
 (progressive.noise_from_state, select_active); rtp_normalize_counts against
@@ -15,68 +15,26 @@ import numpy as np
 import pytest
 
 from _adaptive_ref import F, active_ref, finite_ref, noise_ref, spread_ref
-from test_abi import _agrees, _c_class, _prototypes
+from _abi import prototypes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "rtp_adaptive.h")
+HEADER = "include/rtp_adaptive.h"
 EPS = 2.0 ** -24
-
-
-def _adaptive_prototypes():
-    """include/rtp_adaptive.h's functions in its order: name -> (return type, [argument declarations])."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    protos = {}
-    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(rtp_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", src):
-        args = [a.strip() for a in args.split(",")]
-        protos[name] = (" ".join(ret.split()), [] if args == ["void"] else args)
-    return protos
-
-
-def test_adaptive_table_matches_its_header():
-    """adaptive.SIGNATURES against include/rtp_adaptive.h: count, order, each
-    argument's class and the return class, as test_abi does for rtp.h."""
-    from raytracingtherestofyourlife_amd import adaptive
-
-    protos = _adaptive_prototypes()
-    assert len(protos) == 8
-    assert list(protos) == list(adaptive.SIGNATURES), "the table is in the header's order"
-    bad = []
-    for name, (ret, args) in protos.items():
-        restype, argtypes = adaptive.SIGNATURES[name]
-        if ret != "rtp_status" or restype is not ctypes.c_int32:
-            bad.append(f"{name}: returns {ret}, table {restype}")
-        if len(argtypes) != len(args):
-            bad.append(f"{name}: {len(args)} arguments, table {len(argtypes)}")
-            continue
-        for k, (decl, ct) in enumerate(zip(args, argtypes)):
-            base, depth = _c_class(decl)
-            if base == "rtp_refine_params":  # this header's own struct: a typed pointer, never void*
-                ok = depth == 1 and ct is ctypes.POINTER(adaptive.RtpRefineParams)
-            else:
-                ok = _agrees(ct, base, depth)
-            if not ok:
-                bad.append(f"{name}: argument {k} `{decl}`, table {ct}")
-    assert not bad, "\n".join(bad)
-    fields = [(n, t) for n, t in adaptive.RtpRefineParams._fields_]
-    assert fields == [("threshold", ctypes.c_float), ("spp", ctypes.c_int32), ("max_spp", ctypes.c_int32)]
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef struct \{(.*?)\} rtp_refine_params;", src, flags=re.S).group(1)
-    assert re.findall(r"(\w+)\s+(\w+);", body) == [("float", "threshold"), ("int32_t", "spp"), ("int32_t", "max_spp")]
-    L = adaptive.lib()
-    for name, (restype, argtypes) in adaptive.SIGNATURES.items():
-        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
 
 
 def test_library_exports_the_adaptive_symbols_and_rtp_h_is_unchanged():
     import raytracingtherestofyourlife_amd as rtp
-    from raytracingtherestofyourlife_amd import _lib, adaptive
+    from raytracingtherestofyourlife_amd import _lib
 
     out = subprocess.run(["nm", "-D", "--defined-only", rtp.LIB_PATH], capture_output=True, text=True).stdout
-    for n in _adaptive_prototypes():
+    adaptive = prototypes(HEADER)
+    assert list(adaptive) == list(_lib.SIGNATURES[HEADER])
+    for n in adaptive:
         assert re.search(rf"\bT {n}$", out, flags=re.M), n
-    assert len(_prototypes()) == 40  # include/rtp.h keeps its prototypes ...
-    assert not set(adaptive.SIGNATURES) & set(_lib.SIGNATURES)  # ... and _lib its table
-    assert '#include "rtp.h"' in open(HEADER).read()
+    assert len(prototypes("include/rtp.h")) == 40  # include/rtp.h keeps its prototypes ...
+    assert not set(adaptive) & set(_lib.SIGNATURES["include/rtp.h"])  # ... and _lib its group of them
+    assert not set(adaptive) & set(_lib.EXPORTED_SYMBOLS)
+    assert '#include "rtp.h"' in open(os.path.join(ROOT, HEADER)).read()
 
 
 def test_progressive_render_has_the_device_methods():

@@ -415,7 +415,7 @@ def test_gpu_refine_refusals(device, monkeypatch):
     from raytracingtherestofyourlife_amd import _lib, adaptive
 
     device.set_cornell_box(0)
-    L = adaptive.lib()
+    L = device._L
     nx, ny = 16, 8
     n = nx * ny
     td = torch.device("cuda", device.device)

@@ -10,7 +10,6 @@ bit: rgb sums (NaN-aware), final RNG states and live-bounce counts.
 Reference: MapperPathTracer.cxx:278-350 (the per-pixel sample loop)."""
 from __future__ import annotations
 
-import ctypes
 import os
 
 import numpy as np
@@ -31,10 +30,7 @@ def _load(name):
 def _steal_waves(npix: int, bvh: int) -> int:
     from raytracingtherestofyourlife_amd import _lib
 
-    L = _lib.load()
-    L.rtp_plan_steal.restype = ctypes.c_int
-    L.rtp_plan_steal.argtypes = [ctypes.c_int64, ctypes.c_int]
-    return L.rtp_plan_steal(npix, bvh)
+    return _lib.load().rtp_plan_steal(npix, bvh)
 
 
 @pytest.fixture

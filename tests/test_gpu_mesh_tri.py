@@ -13,7 +13,6 @@ The checks are those of tests/test_gpu_mesh.py and tests/test_gpu_mesh_device.py
 scenes, which tests/_trimeshes.py registers in _meshes.SCENES."""
 from __future__ import annotations
 
-import ctypes
 
 import numpy as np
 import pytest
@@ -53,11 +52,8 @@ def _leave_the_cornell_box(device):
 
 def _records(device, nq):
     """rtp_debug_mesh_records: the stored DevQuads, sorted by the caller's index."""
-    fn = device._L.rtp_debug_mesh_records
-    fn.restype = ctypes.c_int32
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     rec = np.zeros(nq, dtype=DEVQUAD)
-    assert fn(device.handle, nq, rec.ctypes.data) == 0, device._L.rtp_last_error()
+    assert device._L.rtp_debug_mesh_records(device.handle, nq, rec.ctypes.data) == 0, device._L.rtp_last_error()
     assert np.array_equal(np.sort(rec["orig"]), np.arange(nq))
     return rec[np.argsort(rec["orig"])]
 

@@ -23,10 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _plan_steal(npix: int, bvh: int = 0) -> int:
     from raytracingtherestofyourlife_amd import _lib
 
-    L = _lib.load()
-    L.rtp_plan_steal.restype = ctypes.c_int
-    L.rtp_plan_steal.argtypes = [ctypes.c_int64, ctypes.c_int]
-    return L.rtp_plan_steal(npix, bvh)
+    return _lib.load().rtp_plan_steal(npix, bvh)
 
 
 def _cam():

@@ -6,7 +6,6 @@ so the output must equal the generation schedule's (RTP_STEAL=0) bit for
 bit, and the oracle's on any pixel."""
 from __future__ import annotations
 
-import ctypes
 
 import numpy as np
 import pytest
@@ -19,10 +18,7 @@ pytestmark = pytest.mark.gpu
 def _steals(npix: int, bvh: int) -> bool:
     from raytracingtherestofyourlife_amd import _lib
 
-    L = _lib.load()
-    L.rtp_plan_steal.restype = ctypes.c_int
-    L.rtp_plan_steal.argtypes = [ctypes.c_int64, ctypes.c_int]
-    return L.rtp_plan_steal(npix, bvh) > 0
+    return _lib.load().rtp_plan_steal(npix, bvh) > 0
 
 
 def _render_range(device, nx, ny, spp, depth, begin, count, steal, monkeypatch):

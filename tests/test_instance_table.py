@@ -9,7 +9,6 @@ rtp_render_pool<kStats, kBvh, kTiles, kPlan, kSteal, kViews, kResume> and
 rtp_render_pool_lds<kTiles, kSteal> (trailing false arguments left out)."""
 from __future__ import annotations
 
-import ctypes
 import itertools
 
 # (variant, stats, walk, tiles, plan, steal, views, resume) -> kernel
@@ -60,8 +59,6 @@ def _lookup():
     import raytracingtherestofyourlife_amd as rtp
 
     L = rtp.load()
-    L.rtp_instance_name.restype = ctypes.c_char_p
-    L.rtp_instance_name.argtypes = [ctypes.c_int] * 8
 
     def name(mode):
         got = L.rtp_instance_name(*mode)

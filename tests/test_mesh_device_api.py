@@ -14,9 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_signature_table():
     from raytracingtherestofyourlife_amd import _lib
 
-    assert _lib.MESH_SIGNATURES["rtp_set_scene_mesh_device"] == (
+    assert _lib.SIGNATURES["include/rtp_mesh.h"]["rtp_set_scene_mesh_device"] == (
         ctypes.c_int32, [ctypes.c_void_p, ctypes.POINTER(_lib.RtpSceneDesc), ctypes.c_void_p])
-    assert "rtp_set_scene_mesh_device" not in _lib.SIGNATURES
+    assert "rtp_set_scene_mesh_device" not in _lib.SIGNATURES["include/rtp.h"]
+    assert "rtp_set_scene_mesh_device" not in _lib.EXPORTED_SYMBOLS
 
 
 def test_prototype_in_the_public_header():
@@ -34,7 +35,8 @@ def test_symbols_exported():
     L = ctypes.CDLL(build.build())
     for name in ("rtp_set_scene_mesh_device", "rtp_debug_mesh_readback", "rtp_set_scene_mesh", "rtp_mesh_build_host"):
         assert hasattr(L, name), name
-    assert set(_lib.MESH_SIGNATURES) == {"rtp_set_scene_mesh", "rtp_mesh_guarantee", "rtp_set_scene_mesh_device"}
+    assert set(_lib.SIGNATURES["include/rtp_mesh.h"]) == {"rtp_set_scene_mesh", "rtp_mesh_guarantee", "rtp_mesh_counts",
+                                                          "rtp_set_scene_mesh_device"}
 
 
 def test_device_method():

@@ -34,13 +34,7 @@ MAX_OUTSIDE = 0.01
 def _lib():
     import raytracingtherestofyourlife_amd as rtp
 
-    L = rtp.load()
-    L.rtp_mesh_build_host.restype = ctypes.c_int32
-    L.rtp_mesh_build_host.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p] + [ctypes.c_void_p] * 5
-    L.rtp_mesh_leaf_size.restype = ctypes.c_int32
-    L.rtp_instance_name.restype = ctypes.c_char_p
-    L.rtp_instance_name.argtypes = [ctypes.c_int] * 8
-    return L
+    return rtp.load()
 
 
 build = _meshes.build_host
@@ -69,8 +63,12 @@ def test_new_symbols_are_in_the_signature_table():
     from raytracingtherestofyourlife_amd import _lib as lib
 
     i32, vp = ctypes.c_int32, ctypes.c_void_p
-    assert lib.MESH_SIGNATURES["rtp_set_scene_mesh"] == (i32, [vp, ctypes.POINTER(lib.RtpSceneDesc)])
-    assert lib.MESH_SIGNATURES["rtp_mesh_guarantee"] == (i32, [vp, lib.f32p, lib.f32p])
+    mesh = lib.SIGNATURES["include/rtp_mesh.h"]
+    assert mesh["rtp_set_scene_mesh"] == (i32, [vp, ctypes.POINTER(lib.RtpSceneDesc)])
+    assert mesh["rtp_mesh_guarantee"] == (i32, [vp, lib.f32p, lib.f32p])
+    assert not set(mesh) & set(lib.SIGNATURES["include/rtp.h"]) and not set(mesh) & set(lib.EXPORTED_SYMBOLS)
+    rtp_h = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rtp.h")).read()
+    assert not any(name in rtp_h for name in mesh)
     hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "rtp_mesh.h")).read()
     assert "rtp_status rtp_set_scene_mesh(rtp_context* ctx, const rtp_scene_desc* scene);" in hdr
     assert "rtp_status rtp_mesh_guarantee(rtp_context* ctx, float* cos_min, float* reach);" in hdr
@@ -174,9 +172,9 @@ def test_builder_tree(name):
 def test_compact_nodes_round_outward():
     """mesh_compact (the walk's 16-byte nodes): every half-precision box holds its BvhNode's box, an
     unbounded box becomes +-inf, NaN becomes the infinity on its side, and skip / leaf words carry over."""
+    from raytracingtherestofyourlife_amd._lib import ptr
+
     L = _lib()
-    L.rtp_mesh_compact_host.restype = None
-    L.rtp_mesh_compact_host.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     nodes = np.concatenate([built("bent")["nodes"], built("grid65536")["nodes"][:4096]]).copy()
     extra = np.zeros(6, dtype=_meshes.NODE)
     vals = [0.0, -0.0, 65504.0, 65505.0, 1e-8, -1e-8, 2.0 ** -24, 1 + 2.0 ** -11, np.nan, 2.0 ** 100, -2.0 ** 100,
@@ -187,7 +185,7 @@ def test_compact_nodes_round_outward():
         extra["skip"][k] = 7 + k
     nodes = np.concatenate([nodes, extra])
     out = np.zeros((len(nodes), 4), dtype=np.uint32)
-    L.rtp_mesh_compact_host(nodes.ctypes.data, len(nodes), out.ctypes.data)
+    L.rtp_mesh_compact_host(nodes.ctypes.data, len(nodes), ptr(out))
     h = np.ascontiguousarray(out[:, :3]).view(np.uint16).reshape(-1, 6).view(np.float16).astype(np.float64)
     lo, hi = h[:, :3], h[:, 3:]  # (lo.x, lo.y, lo.z, hi.x, hi.y, hi.z: rtp_layout.hpp kCBvhLeafBit)
     nlo, nhi = nodes["lo"].astype(np.float64), nodes["hi"].astype(np.float64)
@@ -326,7 +324,7 @@ def _refused(m, **edit):
     desc, keep = m.desc()
     for k, v in edit.items():
         setattr(desc, k, v)
-    rc = L.rtp_mesh_build_host(ctypes.addressof(desc), 0, 0, None, None, None, None, None, None)
+    rc = L.rtp_mesh_build_host(desc, 0, 0, None, None, None, None, None, None)
     return rc, L.rtp_last_error().decode()
 
 

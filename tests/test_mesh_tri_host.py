@@ -162,14 +162,16 @@ def test_three_ids_a_row_equal_the_repeated_id():
             assert ctypes.string_at(ctypes.addressof(three) + f.offset, f.size) == \
                 ctypes.string_at(ctypes.addressof(four) + f.offset, f.size), name
     # and the builder's outputs, through the descriptors themselves
+    from raytracingtherestofyourlife_amd._lib import ptr
+
     L = tmh._lib()
     outs = []
     for desc in (three, four):
         nodes = np.zeros(2 * 1800, dtype=_meshes.NODE)
         order, boxes, pads = np.zeros(1800, np.int32), np.zeros((1800, 6), F), np.zeros(1800, F)
         nn = ctypes.c_int32(0)
-        assert L.rtp_mesh_build_host(ctypes.addressof(desc), 3, len(nodes), ctypes.addressof(nn), nodes.ctypes.data,
-                                     order.ctypes.data, boxes.ctypes.data, pads.ctypes.data, None) == 0
+        assert L.rtp_mesh_build_host(desc, 3, len(nodes), nn, nodes.ctypes.data, ptr(order), ptr(boxes), ptr(pads),
+                                     None) == 0
         outs.append((nodes[: nn.value].tobytes(), order.tobytes(), boxes.tobytes(), pads.tobytes()))
     assert outs[0] == outs[1]
 
@@ -222,7 +224,10 @@ def test_mesh_counts_is_in_the_header_the_table_and_the_library():
     from raytracingtherestofyourlife_amd import Device
     from raytracingtherestofyourlife_amd import _lib as lib
 
-    assert lib.MESH_TRI_SIGNATURES["rtp_mesh_counts"] == (ctypes.c_int32, [lib.vp, lib.i32p, lib.i32p, lib.i32p])
+    mesh = lib.SIGNATURES["include/rtp_mesh.h"]
+    assert mesh["rtp_mesh_counts"] == (ctypes.c_int32, [lib.vp, lib.i32p, lib.i32p, lib.i32p])
+    assert "rtp_mesh_counts" not in lib.SIGNATURES["include/rtp.h"] and "rtp_mesh_counts" not in lib.EXPORTED_SYMBOLS
+    assert "rtp_mesh_counts" not in open(os.path.join(ROOT, "include", "rtp.h")).read()
     hdr = open(os.path.join(ROOT, "include", "rtp_mesh.h")).read()
     assert ("rtp_status rtp_mesh_counts(rtp_context* ctx, int32_t* n_cells, int32_t* n_triangles, "
             "int32_t* n_unbounded);") in hdr

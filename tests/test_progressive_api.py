@@ -23,7 +23,7 @@ def test_library_exports_resume_symbols():
     for name in ("rtp_render_resume_device", "rtp_render_resume"):
         assert hasattr(L, name), name
         assert name in _lib.EXPORTED_SYMBOLS
-    L.rtp_abi_version.restype = ctypes.c_int32
+    assert not _lib.bind(L)
     assert L.rtp_abi_version() == 3
 
 

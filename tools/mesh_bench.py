@@ -23,7 +23,6 @@ terrain as n bent quads, most of them with the unbounded box (the report's
 "cells", "triangles", "unbounded" are Device.mesh_counts()).
 """
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -56,7 +55,6 @@ if a.reps < 10:
     ap.error("--reps must be at least 10")
 
 L = rtp.load()
-L.rtp_mesh_leaf_size.restype = ctypes.c_int32
 leaf = L.rtp_mesh_leaf_size()
 cam = rtp.default_camera()
 N = a.nx * a.ny

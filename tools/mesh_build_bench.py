@@ -51,8 +51,6 @@ if a.reps < 10:
 os.environ.pop("RTP_MESH_BUILD", None)
 
 L = rtp.load()
-L.rtp_debug_mesh_readback.restype = ctypes.c_int32
-L.rtp_debug_mesh_readback.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32] + [ctypes.c_void_p] * 5
 cam = rtp.default_camera()
 N = a.nx * a.ny
 out = torch.zeros((N, 4), dtype=torch.float32, device="cuda")
@@ -64,7 +62,7 @@ def summary(v):
 
 def nodes_per_octant(dev):
     nn = ctypes.c_int32(0)
-    assert L.rtp_debug_mesh_readback(dev.handle, 0, 0, ctypes.addressof(nn), None, None, None, None) == 0
+    assert L.rtp_debug_mesh_readback(dev.handle, 0, 0, nn, None, None, None, None) == 0
     return nn.value
 
 

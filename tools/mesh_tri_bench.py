@@ -58,9 +58,7 @@ def library(path):
     if not path:
         return rtp.load()
     L = ctypes.CDLL(os.path.abspath(path))
-    for name, (restype, argtypes) in {**_lib.SIGNATURES, **_lib.MESH_SIGNATURES, **_lib.MESH_TRI_SIGNATURES}.items():
-        if hasattr(L, name):  # (a library of an earlier revision lacks the later entry points)
-            getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
+    _lib.bind(L)  # (a library of an earlier revision lacks the later entry points: they stay unbound)
     return L
 
 

@@ -8,12 +8,9 @@ import torch  # noqa: F401  (one HIP runtime)
 from raytracingtherestofyourlife_amd import _lib
 
 L = _lib.load()
-L.rtp_plan_history_lanes.restype = ctypes.c_int64
-L.rtp_plan_history_lanes.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
 STATS = 1 if os.environ.get("RTP_DEBUG_STATS", "")[:1] == "1" else 0  # (the diagnostics build's occupancy)
 for npix in [int(a) for a in sys.argv[1:]] or [640000]:
     for bvh in (0, 1):
         v, w = ctypes.c_int(), ctypes.c_int()
-        lanes = L.rtp_plan_history_lanes(npix, 1000, bvh, STATS, ctypes.byref(v), ctypes.byref(w))
+        lanes = L.rtp_plan_history_lanes(npix, 1000, bvh, STATS, v, w)
         print(f"npix {npix} bvh {bvh}: waves {w.value}, history lanes {lanes}")

@@ -64,18 +64,10 @@ st_sums, st_seed, st_live = buffers()
 st_m2 = torch.zeros(N, dtype=torch.float32, device="cuda")
 fresh_seed = torch.arange(N, dtype=torch.int32, device="cuda")  # seed_base 0
 
-if a.base_lib:  # the baseline library, bound by hand: the package binds one library per process
+if a.base_lib:  # the baseline library beside the package's own, bound with the same table
     P = ctypes.CDLL(os.path.abspath(a.base_lib))
     vp = ctypes.c_void_p
-    P.rtp_last_error.restype = ctypes.c_char_p
-    P.rtp_create.argtypes = [ctypes.c_int32, ctypes.POINTER(vp)]
-    P.rtp_destroy.argtypes, P.rtp_destroy.restype = [vp], None
-    P.rtp_cornell_box.argtypes = [ctypes.c_int32, ctypes.POINTER(_lib.RtpSceneDesc)]
-    P.rtp_set_scene.argtypes = [vp, ctypes.POINTER(_lib.RtpSceneDesc)]
-    P.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
-    P.rtp_render_device.argtypes = [vp, ctypes.POINTER(_lib.RtpCamera), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, vp, vp,
-                                    ctypes.POINTER(_lib.RtpPixelAux), vp, ctypes.POINTER(_lib.RtpStats)]
+    _lib.bind(P)  # (a baseline from an earlier revision lacks the later entry points: they stay unbound)
 
     def ok(rc):
         if rc != 0:

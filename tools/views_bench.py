@@ -58,18 +58,10 @@ out_l = torch.zeros((V * N, 4), dtype=torch.float32, device="cuda")
 stream = torch.cuda.current_stream().cuda_stream
 c_cams = [c.to_c() for c in cams]
 
-if a.loop_lib:  # the baseline library, bound by hand: the package binds one library per process
+if a.loop_lib:  # the baseline library beside the package's own, bound with the same table
     P = ctypes.CDLL(os.path.abspath(a.loop_lib))
     vp = ctypes.c_void_p
-    P.rtp_last_error.restype = ctypes.c_char_p
-    P.rtp_create.argtypes = [ctypes.c_int32, ctypes.POINTER(vp)]
-    P.rtp_destroy.argtypes, P.rtp_destroy.restype = [vp], None
-    P.rtp_cornell_box.argtypes = [ctypes.c_int32, ctypes.POINTER(_lib.RtpSceneDesc)]
-    P.rtp_set_scene.argtypes = [vp, ctypes.POINTER(_lib.RtpSceneDesc)]
-    P.rtp_set_ff_tables.argtypes = [vp, ctypes.c_int32]
-    P.rtp_render_device.argtypes = [vp, ctypes.POINTER(_lib.RtpCamera), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                    ctypes.c_int32, ctypes.c_uint32, ctypes.c_int64, ctypes.c_int64, vp, vp,
-                                    ctypes.POINTER(_lib.RtpPixelAux), vp, ctypes.POINTER(_lib.RtpStats)]
+    _lib.bind(P)  # (a baseline from an earlier revision lacks the later entry points: they stay unbound)
 
     def ok(rc):
         if rc != 0:
